@@ -11,6 +11,10 @@ pipeline order (README.md:140-148) deconvolve (raw coordinates) -> deskew, with 
 of settings/example_deskew_settings.yml (36.17 deg, 0.371, keep_overhang, N=3, overhang_fill mean).
 Rank 0 prints ONE JSON line.  Every rank processes its own position (weak scaling, no data-path
 collective); only the timing barrier and the max-over-ranks reduction use RCCL.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds everything else it
+measures after the timed steps: `ops`, `end_to_end`, `cpu_baseline` (N = 1) and the host-fed leg (N > 1).
+`--dump-outputs DIR` writes what the last timed step returned (see dump_outputs) for comparing builds.
 """
 
 from __future__ import annotations
@@ -445,6 +449,27 @@ def end_to_end(vol_host_u16, psf, rl, iterations, dev, ctx):
     return res
 
 
+DUMP_SAMPLE = 1 << 22          # voxels of the fixed sample of the deskewed volume (16 MB)
+DUMP_PLANE_BYTES = 40 << 20    # the middle output plane, rows cut to this
+
+
+def dump_outputs(out, path):
+    """The deskewed volume the last timed step returned, kept under 64 MB: `deskewed_sample.npy` (float32 at the sorted
+    unique flat indices np.random.default_rng(0).integers(0, numel, DUMP_SAMPLE); the whole volume in order when it is not
+    larger than that), `deskewed_mid_plane.npy` (output plane Z // 2, float32) and `deskewed_shape.npy` (float64 Z, Y, X)."""
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    flat = out.reshape(-1)
+    n = flat.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.default_rng(0).integers(0, n, DUMP_SAMPLE))
+    sample = flat[torch.from_numpy(idx).to(out.device)]
+    np.save(path / "deskewed_sample.npy", sample.to(torch.float32).cpu().numpy())
+    mid = out[out.shape[0] // 2]
+    rows = min(mid.shape[0], DUMP_PLANE_BYTES // (4 * mid.shape[1]))
+    np.save(path / "deskewed_mid_plane.npy", mid[:rows].to(torch.float32).cpu().numpy())
+    np.save(path / "deskewed_shape.npy", np.array(out.shape, dtype=np.float64))
+
+
 def rccl_evidence(dev, world):
     """Every rank's GPU as the collective library sees the job: device name and PCI bus id of each rank, all_gathered over the
     process group bench.py runs its barrier on (RCCL at N > 1).  N ranks on fewer than N distinct GPUs is an error unless the
@@ -470,14 +495,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--shape", type=int, nargs=3, default=[512, 2048, 2048], metavar=("Z", "Y", "X"))
     ap.add_argument("--iterations", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-ops", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure ops, end_to_end and cpu_baseline (N=1) or the host-fed leg (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (rank 0) to DIR/*.npy: a fixed sample of the deskewed volume")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip end_to_end")
+    ap.add_argument("--no-ops", action="store_true", help="with --full: skip ops")
     ap.add_argument("--host-fed", choices=["auto", "on", "off"], default="auto",
                     help="after the resident measurement every rank also runs the overlapped host-fed pipeline (pinned uint16 in, "
-                         "pinned float32 out) so that host-memory / PCIe contention between ranks shows in the N>1 line; auto = on for N>1")
+                         "pinned float32 out) so that host-memory / PCIe contention between ranks shows in the N>1 line; "
+                         "auto = on for N>1 with --full")
     ap.add_argument("--host-fed-units", type=int, default=2)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, local_rank, world = parallel.world_info()
     assert torch.cuda.is_available(), "bench.py needs a GPU (no CPU fallback)"
@@ -530,24 +562,31 @@ def main():
         out = step()
         del out
     rl_ms, dk_ms, fill_ms = [], [], []
+    last = None
     fence()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         out = step()
         # per-kernel HIP-event timings recorded by the library on ITS stream (reading them syncs that stream,
         # which the step's result needs anyway before the next position overwrites the workspace)
         rl_ms.append(ctx.elapsed_ms(_lib.T_RL_ITER))
         dk_ms.append(ctx.elapsed_ms(_lib.T_DESKEW))
         fill_ms.append(ctx.elapsed_ms(_lib.T_FILL))
+        if args.dump_outputs and i == args.steps - 1:
+            last = out
         del out
     fence()
     dt = time.perf_counter() - t0
     dt = parallel.max_over_ranks(dt, dev)
+    if last is not None:
+        if rank == 0:
+            dump_outputs(last, args.dump_outputs)
+        del last
 
-    # host-fed leg on EVERY rank (N > 1 by default): each rank pipelines units from its own pinned uint16 block into its own
+    # host-fed leg on EVERY rank (N > 1 with --full): each rank pipelines units from its own pinned uint16 block into its own
     # pinned float32 blocks — the one thing that can break 8-GPU scaling (8 x 57 GB/s of D2H into one host) is in the line
     host_fed = None
-    if args.host_fed == "on" or (args.host_fed == "auto" and world > 1):
+    if args.host_fed == "on" or (args.host_fed == "auto" and args.full and world > 1):
         # every rank runs the SAME sequence of collectives: a rank that fails locally (pinned memory, HBM) does not leave the
         # others waiting in an all_reduce — the failure is agreed on first, then every rank skips the leg's reductions together
         err, per_unit, steady, tl, legs = None, 0.0, 0.0, None, None
@@ -659,17 +698,17 @@ def main():
         }
         if host_fed is not None:
             result["end_to_end_per_rank"] = host_fed
-        if not args.no_ops and world == 1:
+        if args.full and not args.no_ops and world == 1:
             del vols[1:]
             ctx.release_workspace()
             result["ops"] = ops_suite(vols[0], psf, dev, ctx)
-        if not args.no_end_to_end and world == 1:
+        if args.full and not args.no_end_to_end and world == 1:
             del vols[1:]
             host = torch.empty(shape, dtype=torch.uint16, pin_memory=True)
             host.copy_(vols[0].to(torch.uint16))
             result["end_to_end"] = end_to_end(host, psf, rl_prepared, args.iterations, dev, ctx)
             del host
-        if not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported on rank 0 at N=1 only
             result["cpu_baseline"] = cpu_baseline(args.iterations)
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -5,7 +5,7 @@ tag=$1
 root=${GRAFT_REPO_ROOT:-$PWD}
 o=$root/gpurun_out
 cd $root
-python bench.py > $o/${tag}_bench_default.json 2> $o/${tag}_bench_default.err; tail -c 300 $o/${tag}_bench_default.json; echo
+python bench.py --full > $o/${tag}_bench_default.json 2> $o/${tag}_bench_default.err; tail -c 300 $o/${tag}_bench_default.json; echo
 cd /tmp && export TMPDIR=/tmp
 rm -rf $o/${tag}_prof
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_prof -o b -- python3 $root/bench.py --steps 5 --warmup 2 --no-ops --no-end-to-end --no-cpu-baseline > $o/${tag}_bench_under_profiler.json 2> $o/${tag}_prof.err
