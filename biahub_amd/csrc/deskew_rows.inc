@@ -68,7 +68,8 @@ __global__ void dilate_bits_kernel(const uint32_t* __restrict__ gb, uint32_t* __
     dg[i] = o;
 }
 
-// R[row] = sum_x in[row, x] in float64: one wavefront per row at a time, 16 bytes per lane per load, four rows in flight
+// R[row] = sum_x in[row, x] in float64 (every value converted before it is added: the same sums, to float64 rounding, as the
+// Richardson-Lucy update pass hands over): one wavefront per row at a time, 16 bytes per lane per load, four rows in flight
 template <typename TIN>
 __global__ __launch_bounds__(256) void row_sums_kernel(const TIN* __restrict__ in, double* __restrict__ R, long rows, int X) {
     const int lane = threadIdx.x & 63;
@@ -76,26 +77,26 @@ __global__ __launch_bounds__(256) void row_sums_kernel(const TIN* __restrict__ i
     const bool vec = sizeof(TIN) == 4 && (X & 3) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0;
     for (long row = wave; row < rows; row += nwaves) {
         const TIN* rp = in + row * X;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
         if (vec) {
             const float4* r4 = reinterpret_cast<const float4*>(rp);
             const int n4 = X >> 2;
             int i = lane;
             for (; i + 192 < n4; i += 256) {
                 const float4 a = r4[i], b = r4[i + 64], c = r4[i + 128], d = r4[i + 192];
-                s0 += (a.x + a.y) + (a.z + a.w);
-                s1 += (b.x + b.y) + (b.z + b.w);
-                s2 += (c.x + c.y) + (c.z + c.w);
-                s3 += (d.x + d.y) + (d.z + d.w);
+                s0 += ((double)a.x + (double)a.y) + ((double)a.z + (double)a.w);
+                s1 += ((double)b.x + (double)b.y) + ((double)b.z + (double)b.w);
+                s2 += ((double)c.x + (double)c.y) + ((double)c.z + (double)c.w);
+                s3 += ((double)d.x + (double)d.y) + ((double)d.z + (double)d.w);
             }
             for (; i < n4; i += 64) {
                 const float4 a = r4[i];
-                s0 += (a.x + a.y) + (a.z + a.w);
+                s0 += ((double)a.x + (double)a.y) + ((double)a.z + (double)a.w);
             }
         } else {
-            for (int i = lane; i < X; i += 64) s0 += to_f32(rp[i]);
+            for (int i = lane; i < X; i += 64) s0 += (double)to_f32(rp[i]);
         }
-        double s = ((double)s0 + (double)s1) + ((double)s2 + (double)s3);
+        double s = (s0 + s1) + (s2 + s3);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
         if (lane == 0) R[row] = s;

@@ -851,10 +851,12 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                     x[2 * r + 1] = make_float2(v.z, v.w);
                 }
                 if (MODE == INV_UPDATE && p.rowsum != nullptr) {  // (wave-uniform) the stored row's sum: LG lanes hold it
-                    float s4 = 0.0f;
+                    // summed in float64 from the first value on: each stored float is exact in double, so the row sum is
+                    // est.double().sum(-1) to float64 rounding, and the same as the deskew's own row_sums_kernel computes
+                    double sd = 0.0;
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) s4 += (x[2 * r].x + x[2 * r].y) + (x[2 * r + 1].x + x[2 * r + 1].y);
-                    double sd = (double)s4;
+                    for (int r = 0; r < 8; ++r)
+                        sd += ((double)x[2 * r].x + (double)x[2 * r].y) + ((double)x[2 * r + 1].x + (double)x[2 * r + 1].y);
 #pragma unroll
                     for (int o = LG / 2; o > 0; o >>= 1) sd += __shfl_xor(sd, o, 64);
                     if (l == 0) p.rowsum[row + grp] = sd;

@@ -126,7 +126,7 @@ def deconvolve(
 def richardson_lucy(zyx, psf_zyx, iterations: int = 10, eps: float = 1e-6) -> torch.Tensor:
     """Richardson-Lucy deconvolution of one volume on device (north-star extension, C3).
 
-    Definition (DESIGN.md §2.3): h = psf/sum(psf) centred at the origin, circular boundary;
+    Definition (the C3 comment of oracle/oracle_np.py): h = psf/sum(psf) centred at the origin, circular boundary;
     e0 = max(d,0); e <- max(e * corr_h(d / max(conv_h(e), eps)), 0), ``iterations`` times.
     """
     d, dev = _f32_device(zyx)

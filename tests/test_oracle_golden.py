@@ -378,7 +378,7 @@ def test_oracle_inverse_filter_z_padding_mirrors_edge_planes():
 
 def test_oracle_richardson_lucy_against_spatial_domain_restatement():
     """Richardson-Lucy has no reference implementation (parity unpinned by construction); what the oracle must be is the
-    DEFINITION in DESIGN.md 2.3.  This restates that definition in the spatial domain — circular convolution and correlation as
+    DEFINITION in the C3 comment of oracle/oracle_np.py.  This restates that definition in the spatial domain — circular convolution and correlation as
     explicit sums of rolled copies, no FFT anywhere — and holds the FFT oracle to it, for odd and even PSF extents (the centre
     convention: tap k of an axis of extent K sits at offset k - K // 2)."""
     rng = np.random.default_rng(4)
