@@ -452,14 +452,17 @@ int fftconv_plan(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, ConvPlan** out);
 size_t fftconv_spectrum_elems(const ConvPlan& pl);
 int fftconv_plan_tag(const ConvPlan& pl);
 int fftconv_make_otf(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, cf* otf);
+int fftconv_ztaps_radius(const ConvPlan& pl, int64_t pz);
+size_t fftconv_ztaps_elems(const ConvPlan& pl, int R, bool hermitian);
+int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, int R, cf* work, cf* taps);
 int fftconv_apply(bh_ctx* ctx, const ConvPlan& pl, const float* in, const cf* otf, bool correlate, cf* spec,
                   int epilogue, const float* aux, float eps, float* out);
-int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, cf* spec, int iterations,
+int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, cf* spec, int iterations,
                             float eps, float* est);
 int fftconv_rl_iteration_padded(bh_ctx* ctx, const ConvPlan& pl, const float* est_p, const float* d_p, const cf* otf,
-                                bool otf_real, cf* spec, float eps, float* corr_p);
+                                bool otf_real, int zr, cf* spec, float eps, float* corr_p);
 bool fftconv_rl_wrap_supported(const ConvPlan& pl, const int64_t N[3], const int64_t K[3], const int64_t P[3]);
-int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, cf* spec_a,
+int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, cf* spec_a,
                                  cf* spec_b, float* est_a, float* est_b, const int64_t N[3], const int64_t K[3], int iterations,
                                  float eps, float* out);
 int fftconv_forward(bh_ctx* ctx, const ConvPlan& pl, const float* in, cf* spec);
@@ -532,9 +535,9 @@ static int stage_rl_psf(bh_ctx* ctx, const float* psf, int64_t pz, int64_t py, i
 }
 
 // The iterations of Richardson-Lucy on the fused engine with the transfer function in hand (`otf`: NS complex, or NS floats
-// when `otf_real`): spectrum scratch (auditioned once per allocation), optional event timing, no host synchronisation
-// otherwise.  Shared by the one-shot entry and the prepared handle.
-static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int iterations, float eps,
+// when `otf_real`; with zr >= 0 the compact z taps of that radius instead): spectrum scratch (auditioned once per allocation),
+// optional event timing, no host synchronisation otherwise.  Shared by the one-shot entry and the prepared handle.
+static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, int iterations, float eps,
                          float* out) {
     const size_t NS = fftconv_spectrum_elems(*pl);
     cf* spec;
@@ -558,7 +561,7 @@ static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
         BH_CHECK_HIP(hipEventCreate(&e1));
         BH_CHECK_HIP(hipEventRecord(e0, s));
     }
-    BH_TRY(fftconv_richardson_lucy(ctx, *pl, d, reinterpret_cast<const cf*>(otf), otf_real, spec, iterations, eps, out));
+    BH_TRY(fftconv_richardson_lucy(ctx, *pl, d, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, iterations, eps, out));
     if (e0) {
         BH_CHECK_HIP(hipEventRecord(e1, s));
         BH_CHECK_HIP(hipEventSynchronize(e1));
@@ -637,7 +640,7 @@ static int richardson_lucy_fused(bh_ctx* ctx, const float* d, const float* psf, 
         for (int i = 0; i < 6; ++i) ctx->otf_dims[i] = dims[i];
         ctx->otf_valid = true;
     }
-    return rl_engine_run(ctx, pl, d, real_otf ? (const void*)otf_real : (const void*)otf, real_otf, iterations, eps, out);
+    return rl_engine_run(ctx, pl, d, real_otf ? (const void*)otf_real : (const void*)otf, real_otf, -1, iterations, eps, out);
 }
 
 static bool is_smooth(int64_t n) {  // only the radices hipFFT has native kernels for
@@ -691,7 +694,7 @@ static bool engine_pad_box(const int64_t N[3], const int64_t K[3], int64_t P[3])
 // asks for — by the kernel that also multiplies, clips and rebuilds the wrap-extension for the next iteration.
 // rl_padded_run: the iterations with the transfer function of the box in hand (NS complex, or NS floats when `otf_real`); no
 // host synchronisation unless the context is timing.
-static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, const int64_t N[3],
+static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, const int64_t N[3],
                          const int64_t K[3], const int64_t P[3], int iterations, float eps, float* out) {
     const int64_t VP = P[0] * P[1] * P[2];
     hipStream_t s = ctx->stream;
@@ -738,11 +741,11 @@ static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
     }
     float *cur = a, *nxt = b;
     if (wrap) {  // the last pass stores the result cropped: no crop kernel
-        BH_TRY(fftconv_richardson_lucy_wrap(ctx, *pl, dp, reinterpret_cast<const cf*>(otf), otf_real, spec, spec_b, a, b, N, K,
+        BH_TRY(fftconv_richardson_lucy_wrap(ctx, *pl, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, spec_b, a, b, N, K,
                                             iterations, eps, out));
     } else {
         for (int it = 0; it < iterations; ++it) {
-            BH_TRY(fftconv_rl_iteration_padded(ctx, *pl, cur, dp, reinterpret_cast<const cf*>(otf), otf_real, spec, eps, c));
+            BH_TRY(fftconv_rl_iteration_padded(ctx, *pl, cur, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, eps, c));
             hipLaunchKernelGGL(fold_update_rewrap_kernel, grid2(fold.P), dim3(256), 0, s, (const float*)c, (const float*)cur, nxt, fold);
             std::swap(cur, nxt);
         }
@@ -785,7 +788,7 @@ static int richardson_lucy_engine_padded(bh_ctx* ctx, const float* d, const floa
     ScopedTimer timer(ctx, T_RL_TOTAL);
     BH_TRY(stage_rl_psf(ctx, psf, pz, py, px, P[0], P[1], P[2], a, psum));
     BH_TRY(fftconv_make_otf(ctx, *pl, a, otf));
-    return rl_padded_run(ctx, pl, d, otf, false, N, K, P, iterations, eps, out);
+    return rl_padded_run(ctx, pl, d, otf, false, -1, N, K, P, iterations, eps, out);
 }
 
 // Which transform box and back-end Richardson-Lucy uses for a shape (host logic only; bh_richardson_lucy_plan exports it).
@@ -1153,6 +1156,7 @@ struct bh_rl {
     void* otf = nullptr;       // engine back-ends: NS complex, or NS floats when otf_real (owned, pooled on destroy)
     size_t otf_bytes = 0;
     bool otf_real = false;
+    int zr = -1;               // >= 0: `otf` holds the compact z taps of this radius (fftconv_make_ztaps), the Z passes convolve directly
     float* psf = nullptr;      // library back-end: the PSF itself (the one-shot path rebuilds its library transfer function)
 };
 
@@ -1193,7 +1197,9 @@ int bh_richardson_lucy_create(bh_ctx* ctx, const float* psf, int64_t pz, int64_t
     if (hipMemcpyAsync(hv, dhash, sizeof(hv), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return (set_error("PSF symmetry check failed"), fail(BH_ERR_HIP));
     h->otf_real = (pz & 1) && (py & 1) && (px & 1) && hv[2] == 1ull && getenv("BH_RL_COMPLEX_OTF") == nullptr;
-    h->otf_bytes = NS * (h->otf_real ? sizeof(float) : sizeof(cf));
+    // the PSF's z-extent fits the compiled taps: R + 1 (real) or 2R + 1 planes of taps instead of the Z planes of the transfer function
+    h->zr = fftconv_ztaps_radius(*h->plan, pz);
+    h->otf_bytes = h->zr >= 0 ? fftconv_ztaps_elems(*h->plan, h->zr, h->otf_real) * sizeof(cf) : NS * (h->otf_real ? sizeof(float) : sizeof(cf));
     if ((h->otf = filter_pool_take(ctx->device, h->otf_bytes)) == nullptr &&
         dev_alloc(ctx->device, h->otf_bytes, &h->otf) != hipSuccess) {
         h->otf = nullptr;
@@ -1204,20 +1210,23 @@ int bh_richardson_lucy_create(bh_ctx* ctx, const float* psf, int64_t pz, int64_t
     float* real;
     cf* otf_c = reinterpret_cast<cf*>(h->otf);
     if ((rc = get_scratch(ctx, "fft_real", VP * sizeof(float), (void**)&real)) != BH_OK) return fail(rc);
-    if (h->otf_real) {
+    if (h->otf_real || h->zr >= 0) {
         if ((rc = get_scratch(ctx, "fc_otf", NS * sizeof(cf), (void**)&otf_c)) != BH_OK) return fail(rc);
         ctx->otf_valid = false;  // fc_otf is overwritten: the one-shot path's cache no longer holds
     }
     if ((rc = stage_rl_psf(ctx, psf, pz, py, px, h->box[0], h->box[1], h->box[2], real, psum)) != BH_OK) return fail(rc);
-    if ((rc = fftconv_make_otf(ctx, *h->plan, real, otf_c)) != BH_OK) return fail(rc);
-    if (h->otf_real) {
+    if (h->zr >= 0) {
+        if ((rc = fftconv_make_ztaps(ctx, *h->plan, real, h->otf_real, h->zr, otf_c, reinterpret_cast<cf*>(h->otf))) != BH_OK) return fail(rc);
+    } else if ((rc = fftconv_make_otf(ctx, *h->plan, real, otf_c)) != BH_OK) {
+        return fail(rc);
+    } else if (h->otf_real) {
         hipLaunchKernelGGL(real_part_kernel, grid_for(ctx, (int64_t)NS), dim3(256), 0, s, otf_c, reinterpret_cast<float*>(h->otf),
                            (int64_t)NS);
         if (hipGetLastError() != hipSuccess) return (set_error("real_part_kernel launch failed"), fail(BH_ERR_HIP));
     }
     // the transients of the set-up go back to the driver: the complex transfer function when only its real part is kept (and
     // with it the one-shot path's cache), the padded PSF when the apply path has no use for a real-volume scratch of its own
-    if (h->otf_real && (rc = free_scratch(ctx, "fc_otf")) != BH_OK) return fail(rc);
+    if ((h->otf_real || h->zr >= 0) && (rc = free_scratch(ctx, "fc_otf")) != BH_OK) return fail(rc);
     if (h->backend == BH_RL_ENGINE && (rc = free_scratch(ctx, "fft_real")) != BH_OK) return fail(rc);
     *out = h;
     return BH_OK;
@@ -1255,11 +1264,11 @@ int bh_richardson_lucy_apply_rows(bh_ctx* ctx, const bh_rl* h, const float* in, 
     if (h->backend == BH_RL_ENGINE) {
         // the last update pass can leave the row sums of its result behind (what a deskew with a mean fill wants of this volume)
         if (row_sums) fftconv_arm_rowsums(*h->plan, row_sums);
-        const int st = rl_engine_run(ctx, h->plan, d, h->otf, h->otf_real, iterations, eps, out);
+        const int st = rl_engine_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, iterations, eps, out);
         if (row_sums) *produced = fftconv_rowsums_taken(*h->plan) && st == BH_OK ? 1 : 0;
         return st;
     }
-    return rl_padded_run(ctx, h->plan, d, h->otf, h->otf_real, h->N, h->K, h->box, iterations, eps, out);
+    return rl_padded_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, h->N, h->K, h->box, iterations, eps, out);
 }
 
 int bh_richardson_lucy_destroy(bh_rl* h) {
@@ -1277,6 +1286,13 @@ int bh_richardson_lucy_info(const bh_rl* h, int64_t box[3], int* backend, int* o
     if (backend) *backend = h->backend;
     if (otf_is_real) *otf_is_real = h->otf_real ? 1 : 0;
     if (otf_bytes) *otf_bytes = (uint64_t)h->otf_bytes;
+    return BH_OK;
+}
+
+int bh_richardson_lucy_zpass(const bh_rl* h, int* direct, int* taps) {
+    BH_REQUIRE(h != nullptr, "NULL argument");
+    if (direct) *direct = h->zr >= 0 ? 1 : 0;
+    if (taps) *taps = h->zr >= 0 ? 2 * h->zr + 1 : 0;
     return BH_OK;
 }
 

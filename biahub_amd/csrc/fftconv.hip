@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+#include <utility>
 
 #include <cmath>
 #include <vector>
@@ -889,6 +890,7 @@ namespace xr8 {
 #include "fftconv_colw.inc"
 #include "fftconv_colz.inc"
 #include "fftconv_colz3.inc"
+#include "fftconv_zdirect.inc"
 
 // ================================================================================================
 // host side
@@ -1363,6 +1365,88 @@ int fftconv_make_otf(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, c
     return BH_OK;
 }
 
+// ---- compact z taps (fftconv_zdirect.inc) ----
+// The radius the direct Z pass runs a PSF of z-extent pz at (stage_rl_psf centres it: rows t in [-(pz / 2), pz - 1 - pz / 2]
+// are nonzero, an even extent leaves tap +R zero), rounded up to a compiled radius; -1 when the full transfer function is
+// needed: a PSF too tall for the taps, a column too short for them, or BH_RL_ZDIRECT=0 (read here, i.e. when a handle is created).
+int fftconv_ztaps_radius(const ConvPlan& pl, int64_t pz) {
+    if (getenv("BH_RL_ZDIRECT") && atoi(getenv("BH_RL_ZDIRECT")) == 0) return -1;
+    const int r = (int)(pz / 2);
+    for (int rc : {4, zdirect::RMAX})
+        if (r <= rc) return (pl.d.Z > 2 * rc && pl.d.Z >= rc + zdirect::D) ? rc : -1;
+    return -1;
+}
+
+// complex elements of the taps of radius R: R + 1 Hermitian planes or 2R + 1 general ones, each one z-row of the spectrum
+size_t fftconv_ztaps_elems(const ConvPlan& pl, int R, bool hermitian) {
+    return (size_t)(hermitian ? R + 1 : 2 * R + 1) * pl.d.Y * pl.d.XP;
+}
+
+// taps from Q = the PSF transformed along x and y (z natural), scaled by 2 Z / V: the factor fftconv_make_otf puts in H (2 / V)
+// times the Z of the unnormalised inverse Z transform the direct pass no longer runs.  Hermitian: t = 0..R as
+// (Q(t) + conj(Q(-t))) / 2 — exactly the taps whose transform is Re(H), the real transfer function of the FFT path.
+__global__ void ztaps_extract_kernel(const cf* __restrict__ Q, cf* __restrict__ taps, long ncol, int Z, int R, int hermitian, float scale) {
+    const int nq = hermitian ? R + 1 : 2 * R + 1;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (long)nq * ncol; i += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(i / ncol);
+        const long j = i - (long)k * ncol;
+        cf v;
+        if (hermitian) {
+            const cf a = Q[(long)k * ncol + j], b = Q[(long)((Z - k) % Z) * ncol + j];
+            v = make_float2(0.5f * (a.x + b.x) * scale, 0.5f * (a.y - b.y) * scale);
+        } else {
+            const int t = k - R;
+            v = cscale(Q[(long)((t + Z) % Z) * ncol + j], scale);
+        }
+        taps[i] = v;
+    }
+}
+
+// `work`: a spectrum-sized scratch (fftconv_spectrum_elems), overwritten
+int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, int R, cf* work, cf* taps) {
+    const double V = (double)pl.d.Z * pl.d.Y * pl.d.X;
+    const long ncol = (long)pl.d.Y * pl.d.XP;
+    BH_TRY(launch_x(ctx, pl, false, 0, padded_psf, work, nullptr, nullptr, 0.f));
+    BH_TRY(launch_col(ctx, pl, COL_FWD, false, work, nullptr, 1.f));
+    const long n = (long)(hermitian ? R + 1 : 2 * R + 1) * ncol;
+    hipLaunchKernelGGL(ztaps_extract_kernel, dim3((unsigned)std::min<long>(ceil_div(n, 256), 65535)), dim3(256), 0, ctx->stream, work,
+                       taps, ncol, pl.d.Z, R, hermitian ? 1 : 0, (float)(2.0 * pl.d.Z / V));
+    BH_CHECK_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+template <int R>
+static int launch_zdirect_r(bh_ctx* ctx, const zdirect::Params& p, int mode) {
+    const long nwaves = ceil_div(p.ncol, 64);
+    const dim3 grid((unsigned)ceil_div(nwaves, zdirect::NT / 64));
+    switch (mode) {
+        case COL_FILTER: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_FILTER>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
+        case COL_CONV: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_CONV>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
+        default: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_CORR>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
+    }
+    BH_CHECK_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// The Z pass of one R-L convolution (corr = false) or correlation (corr = true): with the taps of radius zr the direct pass,
+// with the full transfer function (zr < 0) the FFT Z pass launch_col picks
+static int launch_rl_z(bh_ctx* ctx, const ConvPlan& pl, bool corr, bool otf_real, int zr, cf* S, const cf* otf) {
+    const int mode = otf_real ? COL_FILTER : (corr ? COL_CORR : COL_CONV);
+    if (zr < 0) return launch_col(ctx, pl, mode, true, S, otf, 1.f);
+    zdirect::Params p;
+    p.S = S;
+    p.taps = otf;
+    p.ncol = (long)pl.d.Y * pl.d.XP;
+    p.Z = pl.d.Z;
+    BH_REQUIRE(p.Z > 2 * zr && p.Z >= zr + zdirect::D, "internal: %d z taps on columns of %d", 2 * zr + 1, p.Z);
+    switch (zr) {
+        case 4: return launch_zdirect_r<4>(ctx, p, mode);
+        case zdirect::RMAX: return launch_zdirect_r<zdirect::RMAX>(ctx, p, mode);
+        default: BH_REQUIRE(false, "internal: no direct Z pass of radius %d", zr);
+    }
+    return BH_OK;
+}
+
 // out = epilogue( irfft( rfft(in) * OTF or conj(OTF) ) )
 int fftconv_apply(bh_ctx* ctx, const ConvPlan& pl, const float* in, const cf* otf, bool correlate, cf* spec,
                   int epilogue, const float* aux, float eps, float* out) {
@@ -1560,12 +1644,12 @@ static int slab_planes(const ConvPlan& pl) {
 // `est` is output only: the first pass fills it with max(d, 0).
 // With BH_FC_SLAB_MB set, the Yinv -> X -> Yfwd chain between two Z passes runs slab by slab (a few z planes at a time), so
 // that each kernel finds the planes its predecessor just wrote in the 256-MB memory-side cache instead of HBM.
-int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, cf* spec,
+// zr >= 0: `otf` holds the compact z taps of that radius (fftconv_make_ztaps) and the Z passes are direct convolutions.
+int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, cf* spec,
                             int iterations, float eps, float* est) {
     if (iterations <= 0) return BH_OK;
     // otf_real: `otf` holds one float per bin (the transfer function of a point-symmetric PSF); convolution and correlation
     // are then the same real product
-    const int CONV = otf_real ? COL_FILTER : COL_CONV, CORR = otf_real ? COL_FILTER : COL_CORR;
     const int slab = slab_planes(pl);
     if (slab > 0) {
         const int Z = pl.d.Z;
@@ -1576,14 +1660,14 @@ int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, con
         }
         for (int it = 0; it < iterations; ++it) {
             const bool last = it + 1 == iterations;
-            BH_TRY(launch_col(ctx, pl, CONV, true, spec, otf, 1.f));
+            BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec, otf));
             for (int z0 = 0; z0 < Z; z0 += slab) {
                 const int nz = std::min(slab, Z - z0);
                 BH_TRY(launch_col_y_slab(ctx, pl, COL_INV, spec, z0, nz));
                 BH_TRY(launch_x_slab(ctx, pl, true, XE_RATIO, nullptr, spec, nullptr, d, eps, true, z0, nz));
                 BH_TRY(launch_col_y_slab(ctx, pl, COL_FWD, spec, z0, nz));
             }
-            BH_TRY(launch_col(ctx, pl, CORR, true, spec, otf, 1.f));
+            BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec, otf));
             for (int z0 = 0; z0 < Z; z0 += slab) {
                 const int nz = std::min(slab, Z - z0);
                 BH_TRY(launch_col_y_slab(ctx, pl, COL_INV, spec, z0, nz));
@@ -1596,11 +1680,11 @@ int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, con
     BH_TRY(launch_x(ctx, pl, false, 0, d, spec, est, nullptr, 0.f));  // est = max(d, 0) written by the same pass
     for (int it = 0; it < iterations; ++it) {
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-        BH_TRY(launch_col(ctx, pl, CONV, true, spec, otf, 1.f));
+        BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
         BH_TRY(launch_x(ctx, pl, true, XE_RATIO, nullptr, spec, nullptr, d, eps, true));
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-        BH_TRY(launch_col(ctx, pl, CORR, true, spec, otf, 1.f));
+        BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
         BH_TRY(launch_x(ctx, pl, true, XE_UPDATE, nullptr, spec, est, est, eps, it + 1 < iterations));
     }
@@ -1673,15 +1757,14 @@ int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, float* est, size_t by
 // the caller folds its wrapped-around tails back, multiplies, and rebuilds est_p.  9 transform passes (8 when nothing is
 // padded and update -> forward can stay fused).
 int fftconv_rl_iteration_padded(bh_ctx* ctx, const ConvPlan& pl, const float* est_p, const float* d_p, const cf* otf,
-                                bool otf_real, cf* spec, float eps, float* corr_p) {
-    const int COL_CONV = otf_real ? bh::COL_FILTER : bh::COL_CONV, COL_CORR = otf_real ? bh::COL_FILTER : bh::COL_CORR;
+                                bool otf_real, int zr, cf* spec, float eps, float* corr_p) {
     BH_TRY(launch_x(ctx, pl, false, 0, est_p, spec, nullptr, nullptr, 0.f));
     BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-    BH_TRY(launch_col(ctx, pl, COL_CONV, true, spec, otf, 1.f));
+    BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec, otf));
     BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
     BH_TRY(launch_x(ctx, pl, true, XE_RATIO, nullptr, spec, nullptr, d_p, eps, true));
     BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-    BH_TRY(launch_col(ctx, pl, COL_CORR, true, spec, otf, 1.f));
+    BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec, otf));
     BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
     BH_TRY(launch_x(ctx, pl, true, XE_STORE, nullptr, spec, corr_p, nullptr, 0.f));
     return BH_OK;
@@ -1727,10 +1810,9 @@ static int launch_x3_wrap(bh_ctx* ctx, const ConvPlan& pl, int mode, const cf* S
 // d_p: the data on the box, wrap-extended like the estimate (lo below, hi above): the first pass clips it into est_a
 // (e0 = max(d, 0)) and transforms it in one go.  est_a / est_b alternate; the last update is stored straight into `out`, the
 // UNPADDED (N[0], N[1], N[2]) result volume.
-int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, cf* spec_a,
+int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, cf* spec_a,
                                  cf* spec_b, float* est_a, float* est_b, const int64_t N[3], const int64_t K[3], int iterations,
                                  float eps, float* out) {
-    const int CONV = otf_real ? COL_FILTER : COL_CONV, CORR = otf_real ? COL_FILTER : COL_CORR;
     const int64_t P[3] = {pl.d.Z, pl.d.Y, pl.d.X};
     xw::Params::Wrap we[3], wr[3];  // extension of the estimate (lo below, hi above) and of the ratio (hi below, lo above)
     for (int a = 0; a < 3; ++a) {
@@ -1743,11 +1825,11 @@ int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d
     BH_TRY(launch_x(ctx, pl, false, 0, d_p, spec_a, cur, nullptr, 0.f));  // est = max(d, 0) written by the same pass
     for (int it = 0; it < iterations; ++it) {
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec_a, nullptr, 1.f));
-        BH_TRY(launch_col(ctx, pl, CONV, true, spec_a, otf, 1.f));
+        BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec_a, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec_a, nullptr, 1.f));
         BH_TRY(launch_x3_wrap(ctx, pl, xw::FUSED_RATIO_WRAP, spec_a, spec_b, nullptr, d_p, eps, wr[0], wr[2]));
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec_b, nullptr, 1.f));
-        BH_TRY(launch_col(ctx, pl, CORR, true, spec_b, otf, 1.f));
+        BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec_b, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec_b, nullptr, 1.f));
         if (it + 1 == iterations) {  // the last update is needed on the volume's own voxels only: stored cropped
             BH_TRY(launch_x3_wrap(ctx, pl, xw::INV_UPDATE_CROP, spec_b, nullptr, out, cur, eps, we[0], we[2]));

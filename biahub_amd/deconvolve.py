@@ -173,6 +173,11 @@ class PreparedRichardsonLucy:
         self.backend = ("engine", "engine-padded", "library")[backend.value]
         self.otf_is_real = bool(is_real.value)
         self.otf_bytes = int(nbytes.value)
+        direct, taps = ctypes.c_int(), ctypes.c_int()
+        _lib.check(self._ctx.lib.bh_richardson_lucy_zpass(self._handle, ctypes.byref(direct), ctypes.byref(taps)))
+        # "direct": the Z passes convolve along z with `z_taps` compact taps; "fft": the Z FFT with the full transfer function
+        self.z_pass = "direct" if direct.value else "fft"
+        self.z_taps = int(taps.value)
 
     def __call__(self, zyx, iterations: int = 10, eps: float = 1e-6, out: torch.Tensor | None = None,
                  row_sums: torch.Tensor | None = None):

@@ -328,6 +328,10 @@ int bh_richardson_lucy_destroy(bh_rl* handle);
 /* box / backend as bh_richardson_lucy_plan; otf_is_real: the PSF is point-symmetric, one float per bin is kept; any
  * output pointer may be NULL. */
 int bh_richardson_lucy_info(const bh_rl* handle, int64_t box[3], int* backend, int* otf_is_real, uint64_t* otf_bytes);
+/* Which Z pass the handle's engine iterations run: direct = 1 when the PSF's z-extent fits the compact z taps (the Z passes are
+ * direct convolutions along z with `taps` = 2R + 1 taps and the handle keeps those taps instead of the transfer function),
+ * 0 for the FFT Z pass (taps = 0; also the library back-end, and any handle created with BH_RL_ZDIRECT=0).  Either may be NULL. */
+int bh_richardson_lucy_zpass(const bh_rl* handle, int* direct, int* taps);
 
 /* Phase cross-correlation of two equally shaped float32 volumes (biahub/estimate_stabilization.py:199-256
  * phase_cross_corr): corr = irfftn(F1 conj(F2) / norm), norm = 1 | max(|F1 conj F2|, eps) | |F1||F2|.

@@ -50,7 +50,7 @@ def per_iteration(sub):
 
 n_it = rows[[k for k in rows if "xw_kernel<10, 4>" in k][0]][0]  # one fused-ratio launch per iteration
 it = moved("xw_kernel<10, 4>") + moved("xw_kernel<10, 5>")
-col = {k: v for k, v in rows.items() if "col_pass_kernel<" in k or "colw_kernel<" in k or "colz_kernel<" in k}
+col = {k: v for k, v in rows.items() if any(t in k for t in ("col_pass_kernel<", "colw_kernel<", "colz_kernel<", "zdirect_kernel<"))}
 for k, v in col.items():
     per_it = round(v[0] / n_it)          # launches of this kernel per iteration (the OTF build adds a stray call or two)
     it += per_it * (v[1] + v[2]) * 1e9
@@ -71,7 +71,8 @@ rec = {"shape": shape, "unit": "bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, Ki
                  "`python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-end-to-end --no-ops`, summed over the 8 passes of one "
                  "iteration.  The x2 of FETCH_SIZE is calibrated for 16-B-per-lane reads; the real-OTF Z pass reads its multiplier "
                  "with 8 B per lane, which the counter probably tallies exactly, so its fetch (and the iteration total, by up to "
-                 "2 x 4.4 GB at config 2) may be overstated"}
+                 "2 x 4.4 GB at config 2) may be overstated; the direct Z pass (zdirect_kernel) reads 512-B row segments and its "
+                 "doubled fetch matches its model, (Z + R) / Z spectrum reads plus the taps"}
 open(prefix + "_pmc_hbm_traffic.txt", "w").write("\n".join(lines) + "\n")
 json.dump(rec, open(prefix + "_pmc_hbm_traffic.json", "w"), indent=1)
 print("\n".join(lines[:14]))
