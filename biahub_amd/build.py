@@ -12,7 +12,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 INCLUDE = PKG.parent / "include"
 LIB = PKG / "libbhcore.so"
-SOURCES = ["context.hip", "deskew.hip", "fill.hip", "deconv.hip", "fftconv.hip", "affine.hip", "spline.hip", "copy.hip", "regmetric.hip", "flatfield.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
+SOURCES = ["context.hip", "deskew.hip", "fill.hip", "deconv.hip", "fftconv.hip", "affine.hip", "spline.hip", "copy.hip", "regmetric.hip", "flatfield.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "zstd.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
 ARCH = "gfx950"
 
 
@@ -25,7 +25,7 @@ def _hipcc() -> str:
 
 # textual includes of a translation unit (rebuild triggers)
 INCLUDES = {"fftconv.hip": ("fftconv_xpass.inc", "fftconv_xw.inc", "fftconv_x3.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
-            "deskew.hip": ("deskew_rows.inc",)}
+            "deskew.hip": ("deskew_rows.inc",), "zstd.hip": ("zstd_frame.inc", "zstd_block.inc")}
 
 
 def needs_build() -> bool:

@@ -515,6 +515,106 @@ def blosc_lz4_decode_frames_device(frames, out_dev, out_offsets) -> list["BloscH
     return heads
 
 
+def blosc_zstd_stream_table(buf) -> tuple["BloscHeader", np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The zstd streams of a Blosc-1 frame with the zstd inner codec: ``(header, soff, csize, doff, dlen)`` as
+    ``blosc_lz4_stream_table`` returns them (each stream one zstd frame, or a split c-blosc stored raw when ``csize ==
+    dlen``).  Every block start must lie behind the block table and every stream inside ``header.cbytes``; ValueError
+    ("corrupt blosc stream") otherwise.  Host-side parsing only."""
+    h = BloscHeader(buf)
+    if h.codec != "zstd" or h.memcpyed:
+        raise ValueError("not a compressed Blosc frame with the zstd inner codec")
+    mv = memoryview(buf)
+    nblocks = -(-h.nbytes // h.blocksize)
+    if h.cbytes > len(mv) or 16 + 4 * nblocks > h.cbytes:
+        raise ValueError("corrupt blosc stream")
+    bstarts = struct.unpack_from(f"<{nblocks}i", mv, 16)
+    dont_split = bool(h.flags & 0x10)
+    soff, csize, doff, dlen = [], [], [], []
+    for b in range(nblocks):
+        o0 = b * h.blocksize
+        bsize = min(h.blocksize, h.nbytes - o0)
+        split = (not dont_split and h.typesize <= _BLOSC_MAX_SPLITS and h.blocksize // h.typesize >= _BLOSC_MIN_BUFFERSIZE
+                 and bsize == h.blocksize)
+        nsplits = h.typesize if split else 1
+        ne = bsize // nsplits
+        pos = bstarts[b]
+        if pos < 16 + 4 * nblocks:
+            raise ValueError("corrupt blosc stream")
+        for j in range(nsplits):
+            if pos + 4 > h.cbytes:
+                raise ValueError("corrupt blosc stream")
+            (cb,) = struct.unpack_from("<i", mv, pos)
+            pos += 4
+            if cb <= 0 or pos + cb > h.cbytes:
+                raise ValueError("corrupt blosc stream")
+            soff.append(pos)
+            csize.append(cb)
+            doff.append(o0 + j * ne)
+            dlen.append(ne)
+            pos += cb
+    return h, np.asarray(soff, np.uint64), np.asarray(csize, np.uint32), np.asarray(doff, np.uint64), np.asarray(dlen, np.uint32)
+
+
+def _device_streams(fn_name: str, src, tabs, out_dev) -> None:
+    """Launch ``fn_name`` (bh_*_decompress_streams) over the host stream tables ``tabs`` = (soff, csize, doff, dlen)."""
+    import torch
+
+    from . import _lib
+    from .device import get_context, ptr
+
+    dev = out_dev.device
+    dtabs = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32)).to(dev) for a in tabs]
+    ctx = get_context(dev)
+    with torch.cuda.device(dev):
+        _lib.check(getattr(ctx.lib, fn_name)(ctx.handle, ptr(src), ptr(dtabs[0]), ptr(dtabs[1]), ptr(dtabs[2]), ptr(dtabs[3]),
+                                             int(len(tabs[1])), ptr(out_dev)))
+
+
+def blosc_zstd_decode_blocks_device(frame, out_dev) -> "BloscHeader":
+    """The device half of reading a Blosc-zstd frame: ``frame`` is uploaded COMPRESSED and its zstd streams are decoded by
+    ``bh_zstd_decompress_streams`` into ``out_dev`` (uint8 device tensor of ``header.nbytes`` still-permuted bytes;
+    ``unfilter_device`` finishes).  Raises on a corrupt stream."""
+    import torch
+
+    h, soff, csize, doff, dlen = blosc_zstd_stream_table(frame)
+    if out_dev.dtype != torch.uint8 or not out_dev.is_cuda or out_dev.numel() != h.nbytes or not out_dev.is_contiguous():
+        raise ValueError("output must be a contiguous uint8 device tensor of header.nbytes bytes")
+    fr = torch.frombuffer(bytearray(memoryview(frame)[: h.cbytes]), dtype=torch.uint8).to(out_dev.device)
+    _device_streams("bh_zstd_decompress_streams", fr, (soff, csize, doff, dlen), out_dev)
+    return h
+
+
+def blosc_zstd_decode_frames_device(frames, out_dev, out_offsets) -> list["BloscHeader"]:
+    """Several Blosc-zstd frames in ONE pinned upload and ONE launch of ``bh_zstd_decompress_streams``: frame ``k`` decodes to
+    ``out_dev[out_offsets[k]: out_offsets[k] + header.nbytes]`` (uint8 device tensor, still-permuted bytes)."""
+    import torch
+
+    if out_dev.dtype != torch.uint8 or not out_dev.is_cuda or not out_dev.is_contiguous():
+        raise ValueError("output must be a contiguous uint8 device tensor")
+    heads, tabs, sizes, pos = [], [[], [], [], []], [], 0
+    for fr, o in zip(frames, out_offsets):
+        h, soff, csize, doff, dlen = blosc_zstd_stream_table(fr)
+        if o < 0 or o + h.nbytes > out_dev.numel():
+            raise ValueError("frame does not fit the output tensor")
+        heads.append(h)
+        tabs[0].append(soff + np.uint64(pos))
+        tabs[1].append(csize)
+        tabs[2].append(doff + np.uint64(o))
+        tabs[3].append(dlen)
+        sizes.append(h.cbytes)
+        pos += (h.cbytes + 15) & ~15
+    if not heads:
+        return heads
+    host = torch.empty(pos, dtype=torch.uint8, pin_memory=True)
+    hv, q = host.numpy(), 0
+    for fr, nb in zip(frames, sizes):
+        hv[q:q + nb] = np.frombuffer(memoryview(fr)[:nb], np.uint8)
+        q += (nb + 15) & ~15
+    src = host.to(out_dev.device, non_blocking=True)
+    _device_streams("bh_zstd_decompress_streams", src, [np.concatenate(t) for t in tabs], out_dev)
+    return heads
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # zarr compressor configurations -> (decode, encode)
 # ---------------------------------------------------------------------------------------------------------------

@@ -451,9 +451,10 @@ class ZarrArray:
 
     def stage_volume(self, t: int, c: int):
         """The HOST half of ``read_volume_device``, safe on any thread (no GPU call): the (t, c) volume's Blosc chunks are read
-        and entropy-decoded on the I/O threads into one pinned staging block, still permuted (lz4 frames stay compressed: their
-        block codec runs on the GPU).  Returns an opaque object for ``upload_staged``, or None when the layout has no device
-        path (not plane-stack Blosc chunks)."""
+        and entropy-decoded on the I/O threads into one pinned staging block, still permuted (lz4 and zstd frames stay
+        compressed: their block codec runs on the GPU; ``BH_LZ4_DEVICE=0`` / ``BH_ZSTD_DEVICE=0`` keep it on the host).  When
+        every chunk stays compressed no pinned block is allocated (``stage`` is None).  Returns an opaque object for
+        ``upload_staged``, or None when the layout has no device path (not plane-stack Blosc chunks)."""
         import torch
 
         from . import codecs
@@ -466,11 +467,18 @@ class ZarrArray:
             return None
         ct, cc = self.chunks[:2]
         cbytes = self.inner[2] * Y * X * self.dtype.itemsize
-        stage = torch.empty(len(plan) * cbytes, dtype=torch.uint8, pin_memory=True)
-        stage_np = stage.numpy()
         heads: list = [None] * len(plan)
-        frames: dict = {}  # chunks whose LZ4 blocks are decoded on the GPU: the compressed frame travels instead of the raw bytes
+        frames: dict = {}  # chunks whose blocks are decoded on the GPU: the compressed frame travels instead of the raw bytes
         lz4_dev = os.environ.get("BH_LZ4_DEVICE", "1") != "0"
+        zstd_dev = os.environ.get("BH_ZSTD_DEVICE", "1") != "0"
+        holder: list = []  # the pinned staging block, allocated by the first chunk decoded on the host
+        lock = threading.Lock()
+
+        def stage_np():
+            with lock:
+                if not holder:
+                    holder.append(torch.empty(len(plan) * cbytes, dtype=torch.uint8, pin_memory=True))
+                return holder[0].numpy()
 
         def one(i):
             zi, kz, z0, _ = plan[i]
@@ -490,19 +498,21 @@ class ZarrArray:
                     fh.seek(off)
                     buf = fh.read(nb)
             h0 = codecs.BloscHeader(buf)
-            if lz4_dev and h0.codec == "lz4" and not h0.memcpyed and h0.nbytes == cbytes:
+            if ((lz4_dev and h0.codec == "lz4") or (zstd_dev and h0.codec == "zstd")) and not h0.memcpyed and h0.nbytes == cbytes:
                 heads[i] = h0
                 frames[i] = bytes(buf[: h0.cbytes])
                 return
-            h, _ = codecs.blosc_decode_blocks(buf, out=stage_np[i * cbytes:(i + 1) * cbytes])
+            h, _ = codecs.blosc_decode_blocks(buf, out=stage_np()[i * cbytes:(i + 1) * cbytes])
             heads[i] = h
 
         _io_map(one, range(len(plan)))
+        stage = holder[0] if holder else None
         return {"stage": stage, "heads": heads, "frames": frames, "plan": plan, "cbytes": cbytes}
 
     def upload_staged(self, staged, device=None):
-        """The DEVICE half of ``read_volume_device`` (on the thread that owns the GPU context): upload the staging block, decode
-        the LZ4 frames, un-shuffle into the volume.  Returns the (Z, Y, X) device tensor."""
+        """The DEVICE half of ``read_volume_device`` (on the thread that owns the GPU context): upload the staging block (when
+        some chunk was decoded on the host), decode the lz4 and zstd frames (one launch per codec), un-shuffle into the volume.
+        Returns the (Z, Y, X) device tensor."""
         import torch
 
         from . import codecs
@@ -514,12 +524,18 @@ class ZarrArray:
         stage, heads, frames, plan, cbytes = (staged[k] for k in ("stage", "heads", "frames", "plan", "cbytes"))
         out = device_empty((Z, Y, X), tdt, dev)
         out8 = out.view(torch.uint8).reshape(-1)
-        dstage = stage.to(dev, non_blocking=True)
+        if stage is None:  # every chunk arrives compressed: its decode fills the slots, only compressed bytes cross PCIe
+            dstage = torch.empty(len(plan) * cbytes, dtype=torch.uint8, device=dev)
+        else:
+            dstage = stage.to(dev, non_blocking=True)
         plane = Y * X * self.dtype.itemsize
         tmp = None
-        if frames:  # LZ4 blocks -> permuted bytes on the device (csrc/lz4.hip), in the slots the host decoder would have filled:
-            ks = sorted(frames)  # every chunk of the volume in one upload and one launch
-            codecs.blosc_lz4_decode_frames_device([frames[k] for k in ks], dstage, [k * cbytes for k in ks])
+        # LZ4 / zstd blocks -> permuted bytes on the device (csrc/lz4.hip, csrc/zstd.hip), in the slots the host decoder would
+        # have filled: every chunk of one codec in one upload and one launch
+        for name, decode in (("lz4", codecs.blosc_lz4_decode_frames_device), ("zstd", codecs.blosc_zstd_decode_frames_device)):
+            ks = [k for k in sorted(frames) if heads[k].codec == name]
+            if ks:
+                decode([frames[k] for k in ks], dstage, [k * cbytes for k in ks])
         for i, (zi, kz, z0, iz) in enumerate(plan):
             h = heads[i]
             dst = out8[z0 * plane:min(Z, z0 + iz) * plane]

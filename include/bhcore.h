@@ -190,6 +190,13 @@ int bh_blosc_lz4_compress(bh_ctx* ctx, const void* src, uint32_t nframes, uint32
  * BH_ERR_INVALID on a corrupt stream. */
 int bh_lz4_decompress_streams(bh_ctx* ctx, const void* src, const uint64_t* soff, const uint32_t* csize, const uint64_t* doff,
                               const uint32_t* dlen, uint32_t nstreams, void* dst);
+/* zstd frames (RFC 8878) back to bytes on the device, as bh_lz4_decompress_streams does for LZ4: stream i is csize[i] bytes
+ * at src + soff[i] and decodes to dlen[i] bytes at dst + doff[i] (device arrays of nstreams entries; csize == dlen marks a
+ * stream c-blosc stored raw, anything else is one complete zstd frame whose content size, when recorded, must equal dlen).
+ * No dictionaries; a content checksum is skipped.  The result is still permuted: bh_blosc_unfilter finishes.  Synchronises;
+ * BH_ERR_INVALID, naming the first corrupt stream, on a corrupt frame. */
+int bh_zstd_decompress_streams(bh_ctx* ctx, const void* src, const uint64_t* soff, const uint32_t* csize, const uint64_t* doff,
+                               const uint32_t* dlen, uint32_t nstreams, void* dst);
 
 /* The same two permutations on host memory, on the calling thread (no context, no GPU): for volumes that stay on the
  * host.  Re-entrant; callers parallelise over chunks. */

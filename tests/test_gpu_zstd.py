@@ -1,0 +1,168 @@
+"""csrc/zstd.hip: Blosc-zstd chunks decoded on the GPU — c-blosc goldens, pyarrow's zstd across levels and data kinds, hand-built
+frames, corrupt input, the store route and a full-size volume."""
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from biahub_amd import codecs
+
+import zstd_corpus
+
+GOLDEN = Path(__file__).parent / "golden"
+
+
+def _decode_raw_frames(frames, gpu):
+    """zstd frames (one stream each) -> device, one launch; returns the host bytes per frame."""
+    sizes = [len(w) for _, w in frames]
+    src = np.frombuffer(b"".join(f for f, _ in frames), np.uint8)
+    soff = np.cumsum([0] + [len(f) for f, _ in frames[:-1]]).astype(np.uint64)
+    doff = np.cumsum([0] + sizes[:-1]).astype(np.uint64)
+    csize = np.asarray([len(f) for f, _ in frames], np.uint32)
+    dlen = np.asarray(sizes, np.uint32)
+    out = torch.zeros(sum(sizes), dtype=torch.uint8, device=gpu)
+    codecs._device_streams("bh_zstd_decompress_streams", torch.from_numpy(src.copy()).to(gpu), (soff, csize, doff, dlen), out)
+    o = out.cpu().numpy()
+    return [o[int(a):int(a) + n].tobytes() for a, n in zip(doff, sizes)]
+
+
+@pytest.mark.gpu
+def test_zstd_device_decodes_c_blosc_goldens(gpu):
+    z = np.load(GOLDEN / "blosc_streams.npz")
+    done = 0
+    for k in sorted(z.files):
+        if not k.endswith("__blosc"):
+            continue
+        stream = z[k].tobytes()
+        h = codecs.BloscHeader(stream)
+        if h.codec != "zstd" or h.memcpyed or h.nbytes == 0:
+            continue
+        _, want = codecs.blosc_decode_blocks(stream)
+        out = torch.empty(h.nbytes, dtype=torch.uint8, device=gpu)
+        codecs.blosc_zstd_decode_blocks_device(stream, out)
+        assert np.array_equal(out.cpu().numpy(), want), k
+        raw = torch.empty_like(out)
+        codecs.unfilter_device(out, raw, h.blocksize, h.typesize, h.shuffle_mode)
+        assert np.array_equal(raw.cpu().numpy(), z[k[: -len("__blosc")] + "__raw"]), k
+        done += 1
+    assert done >= 25
+
+
+@pytest.mark.gpu
+def test_zstd_device_decodes_pyarrow_corpus_in_one_launch(gpu):
+    """Every data kind x level x block size through codecs.blosc_compress (pyarrow's zstd), all frames in one launch."""
+    frames, want = [], []
+    for data in zstd_corpus.data_kinds().values():
+        for level in zstd_corpus.LEVELS:
+            for bs in zstd_corpus.BLOCKS:
+                fr = codecs.blosc_compress(data, 2, "zstd", level, codecs.BLOSC_BITSHUFFLE, bs)
+                if codecs.BloscHeader(fr).memcpyed:
+                    continue
+                frames.append(fr)
+                want.append(codecs.blosc_decode_blocks(fr)[1])
+    offs = np.cumsum([0] + [w.size for w in want[:-1]]).tolist()
+    out = torch.zeros(sum(w.size for w in want), dtype=torch.uint8, device=gpu)
+    heads = codecs.blosc_zstd_decode_frames_device(frames, out, offs)
+    assert len(heads) == len(frames) >= 80
+    o = out.cpu().numpy()
+    for k, (a, w) in enumerate(zip(offs, want)):
+        assert np.array_equal(o[a:a + w.size], w), k
+    # the same kinds as bare zstd frames (one per block): raw, RLE and compressed blocks, every literals type
+    got = _decode_raw_frames(zstd_corpus.raw_frames(), gpu)
+    for k, ((_, w), g) in enumerate(zip(zstd_corpus.raw_frames(), got)):
+        assert g == w, k
+
+
+@pytest.mark.gpu
+def test_zstd_device_hand_built_frames(gpu):
+    """RLE literals with zero sequences, and a frame mixing raw, RLE and compressed blocks (pyarrow accepts both)."""
+    hf = zstd_corpus.hand_frames()
+    cases = [hf["rle_literals"], hf["mixed_blocks"]]
+    for (frame, want), got in zip(cases, _decode_raw_frames(cases, gpu)):
+        assert got == want
+
+
+def _expect_corrupt(frames, gpu, index):
+    with pytest.raises(ValueError, match=f"corrupt zstd stream {index}"):
+        _decode_raw_frames(frames, gpu)
+
+
+@pytest.mark.gpu
+def test_zstd_device_reports_corrupt_frames(gpu):
+    good = zstd_corpus.raw_frames()
+    camera = [f for f in good if (b"\x28\xb5\x2f\xfd" == f[0][:4])][:4]
+    frame, want = camera[1]
+    # a one-block frame with 4-stream Huffman literals
+    huf = next(fw for fw in good if len(fw[1]) == 32768 and ("literals", "huf4") in zstd_corpus.walk(fw[0]))
+    did = 5 + (0 if (frame[4] >> 5) & 1 else 1)  # the dictionary ID field follows the window descriptor
+    cases = {
+        "truncated": (frame[: len(frame) // 2], want),
+        "dictionary": (frame[:4] + bytes([frame[4] | 1]) + frame[5:did] + b"\x07" + frame[did:], want),
+        "content_size": (frame, want + b"\0"),
+        "offset": zstd_corpus.hand_frames()["offset_past_output"][0:1] + (bytes(7),),
+    }
+    # damaged Huffman tree description: the weights header byte of the first compressed block -> 255 weights of 15
+    hb = bytearray(huf[0])
+    fhd = hb[4]
+    ip = 5 + (0 if (fhd >> 5) & 1 else 1) + ((1 if (fhd >> 5) & 1 else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6))
+    sf = (hb[ip + 3] >> 2) & 3
+    q = ip + 3 + (3, 3, 4, 5)[sf]
+    hb[q:q + 64] = b"\xff" * 64
+    cases["huffman_header"] = (bytes(hb), huf[1])
+    for bad in cases.values():
+        _expect_corrupt([camera[0], bad, camera[2]], gpu, 1)
+    # a good decode afterwards in the same process
+    assert _decode_raw_frames(camera, gpu) == [w for _, w in camera]
+
+
+@pytest.mark.gpu
+def test_zstd_store_routes_are_bit_identical(gpu, tmp_path, monkeypatch):
+    from biahub_amd import io
+
+    shape = (1, 1, 21, 256, 320)  # the last chunk overhangs the array
+    comp = {"id": "blosc", "cname": "zstd", "clevel": 1, "shuffle": 2, "blocksize": 0}
+    io.create_empty_position(tmp_path / "p", ["a"], shape, chunks=(1, 1, 8, 256, 320), dtype=np.uint16, version="0.4", compressor=comp)
+    arr = io.open_ome_zarr(tmp_path / "p").data
+    rng = np.random.default_rng(3)
+    v = (rng.poisson(6, shape[2:]) + 100).astype(np.uint16)
+    arr.write_volume(0, 0, v)
+    host = arr.read_volume(0, 0)
+    assert np.array_equal(host, v)
+    monkeypatch.setenv("BH_ZSTD_DEVICE", "1")
+    staged = arr.stage_volume(0, 0)
+    assert sorted(staged["frames"]) == list(range(len(staged["plan"])))
+    assert staged["stage"] is None  # no raw-size pinned block
+    dev1 = arr.upload_staged(staged, gpu).cpu().numpy()
+    monkeypatch.setenv("BH_ZSTD_DEVICE", "0")
+    staged0 = arr.stage_volume(0, 0)
+    assert not staged0["frames"] and staged0["stage"] is not None
+    dev0 = arr.read_volume_device(0, 0, gpu).cpu().numpy()
+    assert np.array_equal(dev1, host) and np.array_equal(dev0, host)
+
+
+@pytest.mark.gpu
+def test_zstd_device_full_size_volume(gpu):
+    """537 MB of uint16 in c-blosc's 32-KiB zstd blocks: ~16 K frames in one launch."""
+    Z, Y, X = 256, 1024, 1024
+    rng = np.random.default_rng(5)
+    plane = (100 + rng.poisson(20, (Y, X))).astype(np.uint16)
+    cz = 32
+    frames, offs = [], []
+    for z0 in range(0, Z, cz):
+        chunk = np.roll(plane, z0, axis=1)[None].repeat(cz, 0) + np.arange(cz, dtype=np.uint16)[:, None, None]
+        frames.append(codecs.blosc_compress(chunk.view(np.uint8).reshape(-1), 2, "zstd", 1, codecs.BLOSC_BITSHUFFLE, 32768))
+        offs.append(z0 * Y * X * 2)
+    h = codecs.BloscHeader(frames[0])
+    nstreams = sum(len(codecs.blosc_zstd_stream_table(f)[2]) for f in frames)
+    assert nstreams >= 16000
+    out = torch.empty(Z * Y * X * 2, dtype=torch.uint8, device=gpu)
+    codecs.blosc_zstd_decode_frames_device(frames, out, offs)
+    vol = torch.empty_like(out)
+    cb = h.nbytes
+    for k in range(len(frames)):
+        codecs.unfilter_device(out[k * cb:(k + 1) * cb], vol[k * cb:(k + 1) * cb], h.blocksize, 2, h.shuffle_mode)
+    got = vol.view(torch.int16).view(Z, Y, X).cpu().numpy().view(np.uint16)
+    for z0 in range(0, Z, cz):
+        want = np.roll(plane, z0, axis=1)[None].repeat(cz, 0) + np.arange(cz, dtype=np.uint16)[:, None, None]
+        assert np.array_equal(got[z0:z0 + cz], want), z0
