@@ -21,6 +21,7 @@ INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC = 0, 1, 3
 BOUNDARY_ITK, BOUNDARY_SCIPY_CONSTANT, BOUNDARY_ZEROS = 0, 1, 2
 PCC_NORM = {None: 0, "magnitude": 1, "classic": 2}
 FILTER_F32, FILTER_BF16 = 0, 1
+DS_STRIDE, DS_MEAN, DS_MIN, DS_MAX, DS_MEDIAN, DS_MODE = range(6)
 (T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD) = range(9)
 
 _i64, _f64, _f32, _int, _vp = C.c_int64, C.c_double, C.c_float, C.c_int, C.c_void_p
@@ -44,6 +45,7 @@ SIGNATURES = {
     "bh_flat_field": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp, _vp, C.POINTER(_f64)]),
     "bh_bin_reduce": (_int, [_vp, _vp, _int, _i64, _i64, _i64, C.POINTER(_int), _int, _vp, C.POINTER(_f32)]),
     "bh_bin_finish": (_int, [_vp, _vp, _i64, _int, _f32, _f32, _f32, _int, _vp]),
+    "bh_pyramid_downsample": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _int, C.POINTER(_vp)]),
     "bh_valid_mask": (_int, [_vp, _vp, _int, _i64, _vp, C.POINTER(C.c_uint64)]),
     "bh_bits_and": (_int, [_vp, _vp, _vp, _i64]),
     "bh_bits_unpack": (_int, [_vp, _vp, _i64, _vp]),

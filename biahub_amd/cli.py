@@ -830,6 +830,37 @@ def flip_cli(input_position_dirpaths, x, y):
                 arr[t, c] = flip_zyx(arr[t, c], x=x, y=y)
 
 
+@cli.command("pyramid")
+@click.option("--input-position-dirpaths", "-i", multiple=True, required=True, callback=_positions,
+              help='Paths to input positions, e.g. "input.zarr/*/*/*"; they are modified in place')
+@click.option("--sbatch-filepath", "-sb", default=None, type=click.Path(exists=True),
+              help="Accepted for compatibility; Slurm parameters are parsed and ignored.")
+@click.option("--local", "-l", is_flag=True, default=False, help="Accepted for compatibility: this build always runs in-process.")
+@click.option("--levels", "-lv", type=int, default=4, show_default=True,
+              help="Total number of resolution levels including level 0. E.g., levels=4 creates 0, 1, 2, 3.")
+@click.option("--method", "-m", type=click.Choice(["stride", "median", "mode", "mean", "min", "max"]), default="mean",
+              show_default=True, help="Downsampling method to use.")
+def pyramid_cli(input_position_dirpaths, sbatch_filepath, local, levels, method):
+    """Create multi-scale pyramids for OME-Zarr positions, in place (reference: ``biahub pyramid``, pyramid.py:43-126): arrays
+    "1".."levels-1", each halving Z, Y and X of the one before it, computed on the GPU."""
+    from .pyramid import pyramid
+
+    if levels <= 1:
+        click.echo("No pyramid levels to create (levels must be > 1).")
+        return
+    with open_ome_zarr(input_position_dirpaths[0]) as ds:
+        T, C, Z, Y, X = ds.data.shape
+    minutes, cpus, gb = estimate_resources((T, C, Z, Y, X), ram_multiplier=5)
+    echo_resources(cpus, cpus * gb, minutes)
+    if sbatch_filepath:
+        sbatch_to_submitit(sbatch_filepath)
+    _resolve_cluster(None, local=True)
+    pos = Path(input_position_dirpaths[0]).resolve()
+    log_parent = pos.parents[3] if len(pos.parents) > 3 else pos.parent  # next to the plate (row/col/fov below it)
+    _run_positions("pyramid", input_position_dirpaths, input_position_dirpaths,
+                   lambda src, dst: pyramid(src, levels=levels, method=method), log_parent)
+
+
 def main(argv=None):
     argv = expand_eat_all(list(sys.argv[1:] if argv is None else argv))
     return cli.main(args=argv, standalone_mode=True)

@@ -809,6 +809,141 @@ class Position:
         self.zattrs.update(extra)
         _write_group(self.path, self.zarr_format, self.zattrs, self.version)
 
+    # ---- multiscale levels (iohub's Position.initialize_pyramid / compute_pyramid) --------------------
+    def initialize_pyramid(self, levels: int) -> None:
+        """Create empty arrays "1".."levels-1" and list them in ``multiscales[0].datasets``; no voxel is read or written.
+
+        Array "k" has shape (T, C, ceil(n / 2^k)...), chunks ceil(chunk_0 / 2^k) on every axis, level 0's compressor or v3
+        codecs (and shards ratio), and fill value 0; its dataset entry carries level 0's transforms with the Z, Y and X scales
+        multiplied by 2^k (a translation is copied).  Arrays numbered ``levels`` and above, left by an earlier run, are deleted
+        with their dataset entries.  Level 0's files are not touched."""
+        import copy
+        import shutil
+
+        from .pyramid import level_shapes
+
+        levels = int(levels)
+        if levels < 1:
+            raise ValueError(f"levels = {levels}: the pyramid has at least level 0")
+        if self.data is None:
+            raise ValueError(f"{self.path} has no array '0' to build a pyramid from")
+        a0 = self.data
+        meta_file = ".zarray" if a0.zarr_format == 2 else "zarr.json"
+        meta0 = json.loads((a0.path / meta_file).read_text())
+        T, C = a0.shape[:2]
+        for child in self.path.iterdir():  # every earlier level goes: 1..levels-1 are rebuilt, the rest would be stale
+            if child.name.isdigit() and child.name == str(int(child.name)) and int(child.name) >= 1 and self._is_array(child):
+                shutil.rmtree(child)
+        shapes = level_shapes(a0.shape[2:], levels)
+        ratio = [c // i for c, i in zip(a0.chunks, a0.inner)]
+        for k in range(1, levels):
+            f = 1 << k
+            inner = [-(-int(c) // f) for c in a0.inner]
+            meta = copy.deepcopy(meta0)
+            meta["shape"] = [int(T), int(C), *shapes[k]]
+            meta["fill_value"] = 0
+            if a0.zarr_format == 2:
+                meta["chunks"] = inner
+            else:
+                meta["chunk_grid"]["configuration"]["chunk_shape"] = [i * r for i, r in zip(inner, ratio)]
+                for codec in meta["codecs"]:
+                    if codec.get("name") == "sharding_indexed":
+                        codec["configuration"]["chunk_shape"] = inner
+            (self.path / str(k)).mkdir()
+            _write_json(self.path / str(k) / meta_file, meta)
+        ms = copy.deepcopy(self.zattrs["multiscales"])
+        ds0 = next(d for d in ms[0]["datasets"] if str(d.get("path")) == "0")
+        datasets = [ds0]
+        for k in range(1, levels):
+            trs = []
+            for tr in ds0.get("coordinateTransformations", []):
+                tr = copy.deepcopy(tr)
+                if tr.get("type") == "scale":
+                    tr["scale"] = list(tr["scale"][:-3]) + [v * (1 << k) for v in tr["scale"][-3:]]
+                trs.append(tr)
+            datasets.append({"path": str(k), "coordinateTransformations": trs})
+        ms[0]["datasets"] = datasets
+        self.update_zattrs({"multiscales": ms})
+
+    def compute_pyramid(self, levels: int, method: str = "mean") -> None:
+        """Initialise levels 1..levels-1 (``initialize_pyramid``) and fill them on the GPU, one (t, c) volume at a time: level 0
+        is read through the device route (``stage_volume`` + ``upload_staged``), one chain of ``bh_pyramid_downsample`` calls
+        makes every level (``pyramid.downsample_pyramid``), and each level is stored with ``encode_volume_device``.  A reader
+        thread stages the next volume and a writer thread runs the host halves (entropy coding, file writes) while this thread
+        drives the GPU.  There is no CPU path: without a GPU this raises before the store is touched.
+        ``BH_PIPE_TIMING=1`` prints the seconds of each stage per volume on stderr (it synchronises the GPU between stages)."""
+        import sys
+        import time
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+
+        from .device import resolve_device, volume_pool
+        from .pyramid import check_args, downsample_pyramid
+
+        if self.data is None:
+            raise ValueError(f"{self.path} has no array '0' to build a pyramid from")
+        check_args(self.data.dtype, levels, method)
+        dev = resolve_device("cuda")
+        self.initialize_pyramid(levels)
+        if int(levels) == 1:
+            return
+        import torch
+
+        src = self.data
+        arrs = [ZarrArray(self.path / str(k)) for k in range(1, int(levels))]
+        T, C = src.shape[:2]
+        units = [(t, c) for t in range(T) for c in range(C)]
+        timing = {"read": [], "upload": [], "kernel": [], "encode": [], "write": []} if os.environ.get("BH_PIPE_TIMING") else None
+
+        def clocked(name, fn, *args):
+            t0 = time.perf_counter()
+            r = fn(*args)
+            if timing is not None:
+                timing[name].append(time.perf_counter() - t0)
+            return r
+
+        def load(u):
+            staged = src.stage_volume(*u)
+            return (staged, None) if staged is not None else (None, src.read_volume(*u))
+
+        def upload(staged, host):
+            if staged is not None:
+                return src.upload_staged(staged, dev)
+            with volume_pool(dev):
+                return torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+
+        def synced(fn, *args):
+            r = fn(*args)
+            if timing is not None:
+                torch.cuda.synchronize(dev)
+            return r
+
+        def write(commits):
+            for commit in commits:
+                commit()
+
+        with ThreadPoolExecutor(1, thread_name_prefix="bh-pyr-r") as reader, \
+                ThreadPoolExecutor(1, thread_name_prefix="bh-pyr-w") as writer:
+            nxt = reader.submit(clocked, "read", load, units[0])
+            pending = deque()
+            for i, (t, c) in enumerate(units):
+                staged, host = nxt.result()
+                nxt = reader.submit(clocked, "read", load, units[i + 1]) if i + 1 < len(units) else None
+                vol = clocked("upload", synced, upload, staged, host)
+                del staged, host
+                lv = clocked("kernel", synced, downsample_pyramid, vol, levels, method)
+                del vol
+                commits = clocked("encode", lambda: [a.encode_volume_device(t, c, v) for a, v in zip(arrs, lv)])
+                del lv
+                pending.append(writer.submit(clocked, "write", write, commits))
+                while len(pending) > 2:  # bound the encoded levels held in host memory
+                    pending.popleft().result()
+            while pending:
+                pending.popleft().result()
+        if timing is not None:
+            print(f"pyramid timing {self.path}: " + ", ".join(
+                f"{k} " + "/".join(f"{x:.3f}" for x in v) for k, v in timing.items() if v) + " s", file=sys.stderr, flush=True)
+
 
 def open_ome_zarr(path, mode: str = "r", layout: str = "auto") -> Position:
     """Open one position (``layout="fov"`` and HCS positions look the same on disk below the FOV group)."""

@@ -11,6 +11,7 @@
  *                          <- biahub/flat_field.py:101-120 flat_field_zyx, :56-99 _median_tiled (np.median, axis 0)
  *   bh_bin_reduce, bh_bin_finish
  *                          <- biahub/process_data.py:29-105 binning_czyx
+ *   bh_pyramid_downsample  <- biahub/pyramid.py:19-40 pyramid (iohub's Position.compute_pyramid)
  *   bh_valid_mask, bh_bits_and, bh_bits_unpack
  *                          <- biahub/estimate_crop.py:58-94 estimate_crop_one_position (masks, counts, their AND)
  *   bh_blosc_unfilter, bh_blosc_filter
@@ -151,6 +152,20 @@ int bh_bin_reduce(bh_ctx* ctx, const void* in, int in_dtype, int64_t Z, int64_t 
  * ndarray.astype; out_dtype is one of the BH_DT_* codes. */
 int bh_bin_finish(bh_ctx* ctx, const float* v, int64_t n, int apply, float sub, float mul, float div, int out_dtype,
                   void* out);
+
+/* ---- multiscale pyramid levels (biahub/pyramid.py: iohub's Position.compute_pyramid) ---------------- */
+#define BH_DS_STRIDE 0 /* the block's first element: level k = level0[::2^k, ::2^k, ::2^k]                          */
+#define BH_DS_MEAN 1   /* integers: exact sum / count, to nearest, ties to even; float32: float64 sum in (z, y, x) order */
+#define BH_DS_MIN 2
+#define BH_DS_MAX 3
+#define BH_DS_MEDIAN 4 /* the lower median: sorted block[(count - 1) / 2]                                              */
+#define BH_DS_MODE 5   /* the most frequent value, the smallest among ties                                              */
+/* out[k-1] (device, (ceil(Z / 2^k), ceil(Y / 2^k), ceil(X / 2^k)) of the input dtype) receives level k, k = 1..n.  Level k
+ * voxel (z, y, x) reduces the block [2z, min(2z + 2, n)) x [2y, ...) x [2x, ...) of level k-1 as stored (1, 2, 4 or 8
+ * elements).  in (device, (Z, Y, X), BH_DT_*) is only read.  BH_ERR_INVALID for an unknown dtype or method, n < 1, a
+ * non-positive extent or a null pointer, before any device call.  Stream-ordered, no allocation, does not synchronise. */
+int bh_pyramid_downsample(bh_ctx* ctx, const void* in, int dtype, int64_t Z, int64_t Y, int64_t X, int method, int n,
+                          void* const* out);
 
 /* ---- validity masks (crop estimation, biahub/estimate_crop.py:58-94) -------------------- */
 /* bits: ceil(n / 64) * 2 words on the device; voxel i -> bit i % 32 of word i / 32, set when the voxel is neither 0 nor
