@@ -12,7 +12,9 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 INCLUDE = PKG.parent / "include"
 LIB = PKG / "libbhcore.so"
-SOURCES = ["context.hip", "deskew.hip", "fill.hip", "deconv.hip", "fftconv.hip", "affine.hip", "spline.hip", "copy.hip", "regmetric.hip", "flatfield.hip", "psf.hip", "binning.hip", "pyramid.hip", "codec.hip", "lz4.hip", "zstd.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
+# longest compiles first (the pool below starts sources in this order): pyramid.hip alone takes longer than any other file, then
+# the kernel families of the FFT engine
+SOURCES = ["pyramid.hip", "fftconv_col.hip", "fftconv_xtile.hip", "fftconv_xw.hip", "fftconv_colreg.hip", "deskew.hip", "affine.hip", "fftconv.hip", "context.hip", "fill.hip", "deconv.hip", "spline.hip", "copy.hip", "regmetric.hip", "flatfield.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "zstd.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
 ARCH = "gfx950"
 
 
@@ -24,7 +26,10 @@ def _hipcc() -> str:
 
 
 # textual includes of a translation unit (rebuild triggers)
-INCLUDES = {"fftconv.hip": ("fftconv_xpass.inc", "fftconv_xw.inc", "fftconv_x3.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
+_FC = ("fftconv.hpp", "fftconv_dev.hpp")
+INCLUDES = {"fftconv.hip": _FC, "fftconv_col.hip": _FC, "fftconv_xtile.hip": _FC + ("fftconv_xpass.inc",), "fftconv_xw.hip": _FC + ("fftconv_xw.inc", "fftconv_x3.inc"),
+            "fftconv_colreg.hip": _FC + ("fftconv_xw.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"),
+            "deconv.hip": ("fftconv.hpp",), "invtf.hip": ("fftconv.hpp",), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
             "deskew.hip": ("deskew_rows.inc",), "zstd.hip": ("zstd_frame.inc", "zstd_block.inc")}
 
 

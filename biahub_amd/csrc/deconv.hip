@@ -9,13 +9,12 @@
 // All spectra are Hermitian halves (Z, Y, X/2+1) of complex64; H is real and even, so the
 // half-spectrum filter is exactly the reference's full-spectrum product.
 #include "common.hpp"
+#include "fftconv.hpp"
 
 #include <cstdlib>
 #include <cstring>
 
 namespace bh {
-
-typedef float2 cf;
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -441,39 +440,6 @@ static inline dim3 grid_for(bh_ctx* ctx, int64_t n, int tb = 256) {
 
 static void pad_before(int64_t p, int64_t S, int* before) { *before = (int)((S - p) / 2); }
 
-// fused FFT-convolution engine (fftconv.hip)
-struct ConvPlan;
-bool fftconv_supported(int64_t Z, int64_t Y, int64_t X);
-bool fftconv_supported_ex(int64_t Z, int64_t Y, int64_t X, bool radix3);
-bool fftconv_rows_wave_private(int64_t Y, int64_t X);
-void fftconv_arm_rowsums(ConvPlan& pl, double* dst);
-bool fftconv_rowsums_taken(ConvPlan& pl);
-int fftconv_plan(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, ConvPlan** out);
-size_t fftconv_spectrum_elems(const ConvPlan& pl);
-int fftconv_plan_tag(const ConvPlan& pl);
-int fftconv_make_otf(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, cf* otf);
-int fftconv_ztaps_radius(const ConvPlan& pl, int64_t pz);
-size_t fftconv_ztaps_elems(const ConvPlan& pl, int R, bool hermitian);
-int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, int R, cf* work, cf* taps);
-int fftconv_apply(bh_ctx* ctx, const ConvPlan& pl, const float* in, const cf* otf, bool correlate, cf* spec,
-                  int epilogue, const float* aux, float eps, float* out);
-int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, cf* spec, int iterations,
-                            float eps, float* est);
-int fftconv_rl_iteration_padded(bh_ctx* ctx, const ConvPlan& pl, const float* est_p, const float* d_p, const cf* otf,
-                                bool otf_real, int zr, cf* spec, float eps, float* corr_p);
-bool fftconv_rl_wrap_supported(const ConvPlan& pl, const int64_t N[3], const int64_t K[3], const int64_t P[3]);
-int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, cf* spec_a,
-                                 cf* spec_b, float* est_a, float* est_b, const int64_t N[3], const int64_t K[3], int iterations,
-                                 float eps, float* out);
-int fftconv_forward(bh_ctx* ctx, const ConvPlan& pl, const float* in, cf* spec);
-int fftconv_inverse(bh_ctx* ctx, const ConvPlan& pl, cf* spec, float* out);
-int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, float* est, size_t bytes, cf** spec);
-bool fftconv_pcc_peak_only(const ConvPlan& pl);
-int fftconv_pcc_apply(bh_ctx* ctx, const ConvPlan& pl, const float* img, cf* fixed, bool fixed_is_mov, bool roll, cf* s2, int norm,
-                      float scale, float* corr, ArgMax* partial, int* npartial);
-int fftconv_tikhonov(bh_ctx* ctx, const ConvPlan& pl, const float* in, const float* tf_full, float reg, cf* spec,
-                     float* filt, float* out);
-
 static bool use_fused_engine(int64_t Z, int64_t Y, int64_t X) {
     if (const char* e = getenv("BH_FFT_BACKEND"))
         if (strcmp(e, "hipfft") == 0) return false;
@@ -541,11 +507,8 @@ static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
                          float* out) {
     const size_t NS = fftconv_spectrum_elems(*pl);
     cf* spec;
-    // BH_FC_SPEC_X2=1: the spectrum as the first half of an allocation of twice its size (experiment: sub-ranges of larger
-    // allocations never showed the slow state of the fused update pass) — no audition then
-    static const bool spec_x2 = getenv("BH_FC_SPEC_X2") && atoi(getenv("BH_FC_SPEC_X2")) != 0;
-    BH_TRY(get_scratch(ctx, "fc_spec", (spec_x2 ? 2 : 1) * NS * sizeof(cf), (void**)&spec));
-    if (spec != ctx->spec_tuned && !spec_x2) {  // a new allocation: audition it (fftconv_tune_spectrum)
+    BH_TRY(get_scratch(ctx, "fc_spec", NS * sizeof(cf), (void**)&spec));
+    if (spec != ctx->spec_tuned) {  // a new allocation: audition it (fftconv_tune_spectrum)
         Scratch& sc = ctx->scratch["fc_spec"];
         // the audition may free the allocation it was handed and keep another one: the scratch table must follow it on the
         // error path too, or the next get_scratch("fc_spec") hands out a freed pointer

@@ -1,4 +1,4 @@
-// Register-stage column passes of the fused FFT engine (columns of 256, 512 or 1024 points) — included by fftconv.hip.
+// Register-stage column passes of the fused FFT engine (columns of 256, 512 or 1024 points) — included by fftconv_colreg.hip.
 //
 // col_pass_kernel keeps a 128-KiB tile (N rows x W columns) in LDS and runs every radix-4 step of the column transform as
 // an LDS round trip behind a workgroup barrier (5 per transform; the Z pass, forward x OTF x inverse, 9 with its fused
@@ -14,21 +14,8 @@
 // of every exchange access: none, with 128 B of padding per 32 rows).
 namespace colw {
 
-#ifndef BH_COLW_NOSYNC
-#define BH_COLW_NOSYNC 0  // 1: timing probe with the exchange barriers compiled out (wrong results)
-#endif
-#if BH_COLW_NOSYNC
-#define BH_COLW_SYNC() asm volatile("" ::: "memory")
-#else
-#define BH_COLW_SYNC() __syncthreads()
-#endif
-
 #ifndef BH_COLW_NT
 #define BH_COLW_NT 512
-#endif
-#ifndef BH_COLW_XCD
-#define BH_COLW_XCD 0  // 1: every XCD (workgroup index mod 8) walks its own CONTIGUOUS eighth of the tiles, so that neighbouring column
-                       // tiles — the 128-B neighbours of every row segment — meet in one L2 instead of eight (A/B: tools/ab_lib.sh)
 #endif
 constexpr int NT = BH_COLW_NT;       // 512: 8 wavefronts, one workgroup and one 128-KiB tile per CU (256: two workgroups with 64-KiB
                                      // tiles, i.e. half as wide row segments — measured slower, tools/ab_variant.sh)
@@ -110,15 +97,15 @@ __device__ __forceinline__ void forward(cf (&x0)[16], cf (&x1)[16], float4* tile
     xw::reg_fft<4, 0, 1, false>(x1);
     twiddle16<false>(x0, x1, ta, G::N16, rest);
     put<LOGN, 0>(tile, x0, x1, rest, cp);
-    BH_COLW_SYNC();
+    __syncthreads();
     get<LOGN, 1>(tile, x0, x1, rest, cp);
     xw::reg_fft<4, 0, 1, false>(x0);
     xw::reg_fft<4, 0, 1, false>(x1);
     if constexpr (G::LOWBITS > 0) {
         twiddle16<false>(x0, x1, tb, G::NQ, rest % G::NQ);
-        BH_COLW_SYNC();  // every thread has read exchange 1 before anyone writes exchange 2
+        __syncthreads();  // every thread has read exchange 1 before anyone writes exchange 2
         put<LOGN, 1>(tile, x0, x1, rest, cp);
-        BH_COLW_SYNC();
+        __syncthreads();
         get<LOGN, 2>(tile, x0, x1, rest, cp);
         stage_c<LOGN, false>(x0);
         stage_c<LOGN, false>(x1);
@@ -132,15 +119,15 @@ __device__ __forceinline__ void inverse(cf (&x0)[16], cf (&x1)[16], float4* tile
         stage_c<LOGN, true>(x0);
         stage_c<LOGN, true>(x1);
         put<LOGN, 2>(tile, x0, x1, rest, cp);
-        BH_COLW_SYNC();
+        __syncthreads();
         get<LOGN, 1>(tile, x0, x1, rest, cp);
         twiddle16<true>(x0, x1, tb, G::NQ, rest % G::NQ);
     }
     xw::reg_fft<4, 0, 1, true>(x0);
     xw::reg_fft<4, 0, 1, true>(x1);
-    if constexpr (G::LOWBITS > 0) BH_COLW_SYNC();
+    if constexpr (G::LOWBITS > 0) __syncthreads();
     put<LOGN, 1>(tile, x0, x1, rest, cp);
-    BH_COLW_SYNC();
+    __syncthreads();
     get<LOGN, 0>(tile, x0, x1, rest, cp);
     twiddle16<true>(x0, x1, ta, G::N16, rest);
     xw::reg_fft<4, 0, 1, true>(x0);
@@ -181,18 +168,15 @@ __global__ __launch_bounds__(NT, 2) void colw_kernel(ColParams p) {
         for (int r = 0; r < 16; ++r) pre[r] = *reinterpret_cast<const float4*>(src + row_of<LOGN, DLOAD>(rest, r) * rs);
     };
     const int rest0 = tid / G::CPN;
-    const bool xcd = BH_COLW_XCD && (gridDim.x & 7) == 0;
-    const int per_xcd = (ntiles + 7) >> 3;
-    const int tstep = xcd ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    const int tend = xcd ? min(ntiles, ((int)(blockIdx.x & 7) + 1) * per_xcd) : ntiles;
-    int t = xcd ? (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-    if (t < tend) load_rows(t, rest0);
-    for (; t < tend; t += tstep) {
+    const int tstep = (int)gridDim.x;
+    int t = (int)blockIdx.x;
+    if (t < ntiles) load_rows(t, rest0);
+    for (; t < ntiles; t += tstep) {
         // opaque: the row offsets and LDS addresses derived from it are recomputed where they are used instead of being
         // hoisted out of the loop into (three sets of sixteen) long-lived registers
         const int rest = xw::opaque_i(rest0);
         const long base = tile_base(t);
-        const int tn = t + tstep < tend ? t + tstep : t;  // unconditional prefetch (the last round re-reads its tile)
+        const int tn = t + tstep < ntiles ? t + tstep : t;  // unconditional prefetch (the last round re-reads its tile)
         cf x0[16], x1[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(NT, 2) void colw_kernel(ColParams p) {
             }
             asm volatile("" ::: "memory");  // the next tile's rows only now: above, they would sit on top of the multiplier rows
             load_rows(tn, rest);
-            BH_COLW_SYNC();  // exchange 2 of the forward transform has been read by everyone
+            __syncthreads();  // exchange 2 of the forward transform has been read by everyone
             inverse<LOGN>(x0, x1, tile, ta, tb, rest, cp);
         }
         const bool col_ok = ((t % ncoltiles) * G::W + 2 * cp) < XP;
@@ -256,7 +240,7 @@ __global__ __launch_bounds__(NT, 2) void colw_kernel(ColParams p) {
                 *reinterpret_cast<float4*>(p.S + base + row_of<LOGN, DSTORE>(rest, r) * rs) =
                     make_float4(x0[r].x, x0[r].y, x1[r].x, x1[r].y);
         }
-        BH_COLW_SYNC();  // the last exchange of this tile has been read before the next tile writes the buffer
+        __syncthreads();  // the last exchange of this tile has been read before the next tile writes the buffer
     }
 }
 

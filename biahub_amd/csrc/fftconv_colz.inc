@@ -1,5 +1,5 @@
 // Z pass of 512-point columns with radix-8 register stages: forward transform, spectral product, inverse transform of a
-// 512 x 32 column tile in FOUR LDS round trips and four barriers (col_pass_kernel: ten and eleven).  Included by fftconv.hip
+// 512 x 32 column tile in FOUR LDS round trips and four barriers (col_pass_kernel: ten and eleven).  Included by fftconv_colreg.hip
 // (namespace bh).
 //
 // The LDS store path moves ~80 B/clk per CU whatever the store width (MI355X_MICROARCH.md, LDS): a 128-KiB tile costs ~1640
@@ -19,28 +19,10 @@ namespace colz {
                       // workgroups with 64-KiB tiles (128-B row segments; one workgroup's loads under the other's steps) — measured
                       // on the shuffled layout: 5.01 against 4.32 ms per launch (tools/prof_variant.sh), so 32 stays
 #endif
-#ifndef BH_COLZ_PROBE
-#define BH_COLZ_PROBE 0  // timing probes with WRONG results (tools/build_variant.py): bit 0 = no stage arithmetic, bit 1 = no LDS exchanges,
-                         // bit 2 = no multiplier loads, bit 3 = no workgroup barriers inside the tile loop, bit 4 = no tile loads / stores
-#endif
-#ifndef BH_COLZ_ONEXT
-#define BH_COLZ_ONEXT 0  // 1: the multiplier rows of tile t + 1 are requested right behind the spectral product of tile t (their registers
-                         // are free from there on) instead of behind step A of their own tile, where they queue up behind the 128 KiB
-                         // of stores that tile t has just issued and are waited for two steps later
-#endif
 constexpr int N = 512, W = BH_COLZ_W, NT = 32 * W, CP = W / 2;  // rows, complex columns, threads, column pairs (float4) per row
 constexpr int LOGCP = W == 32 ? 4 : 3;
 static_assert(W == 32 || W == 16, "BH_COLZ_W must be 16 or 32");
 constexpr int LDS_BYTES = N * W * 8 + (64 + 8) * 3 * 8;
-
-#define COLZ_SYNC()                                    \
-    do {                                               \
-        if (!(BH_COLZ_PROBE & 8)) __syncthreads();     \
-    } while (0)
-#define COLZ_ARITH(stmt)                    \
-    do {                                    \
-        if (!(BH_COLZ_PROBE & 1)) { stmt; } \
-    } while (0)
 
 struct C2 {  // the two columns of a thread
     cf a, b;
@@ -152,7 +134,7 @@ __device__ __forceinline__ void inv8(C2 (&x)[8], cf w1, cf w2, cf w3) {
 #define BH_COLZ_PKROT 1
 #endif
 typedef float v2f __attribute__((ext_vector_type(2)));
-// (add_mi / add_pi: fftconv.hip)
+// (add_mi / add_pi: fftconv_dev.hpp)
 __device__ __forceinline__ cf cmul_mi(cf a, cf w) {  // a * (-i w) = (a.x w.y + a.y w.x, a.y w.y - a.x w.x)
     v2f av = {a.x, a.y}, wv = {w.x, w.y}, t, r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(t) : "v"(av), "v"(wv));
@@ -336,8 +318,7 @@ __global__ __launch_bounds__(NT, 1024 / NT) void colz_kernel(ColParams p) {
     auto load_tile = [&](long base) {
         const unsigned la = (unsigned)xw::opaque_i((int)laneA);
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            v[u] = (BH_COLZ_PROBE & 16) ? make_float4((float)tid, 1.f, 2.f, 3.f) : *reinterpret_cast<const float4*>(rowA_ptr(base, u) + la);
+        for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(rowA_ptr(base, u) + la);
     };
     float4 o[8];
     auto load_otf = [&](long base) {
@@ -345,9 +326,7 @@ __global__ __launch_bounds__(NT, 1024 / NT) void colz_kernel(ColParams p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const unsigned char* rp = reinterpret_cast<const unsigned char*>(p.otf) + scalar_off((base + (long)(8 * GPW * wave + i) * row_stride) * OB);
-            if (BH_COLZ_PROBE & 4) {
-                o[i] = make_float4(1.f, 1.f, 0.f, 0.f);
-            } else if (MODE == COL_FILTER) {
+            if (MODE == COL_FILTER) {
                 const float2 f = *reinterpret_cast<const float2*>(rp + laneC);
                 o[i] = make_float4(f.x, f.y, 0.f, 0.f);
             } else if (MODE == COL_CONV16) {
@@ -360,10 +339,7 @@ __global__ __launch_bounds__(NT, 1024 / NT) void colz_kernel(ColParams p) {
         }
     };
     long t = blockIdx.x;
-    if (t < ntiles) {
-        load_tile(base_of(cur_ou, cur_ct));
-        if (BH_COLZ_ONEXT) load_otf(base_of(cur_ou, cur_ct));
-    }
+    if (t < ntiles) load_tile(base_of(cur_ou, cur_ct));
     __syncthreads();  // twiddle tables
     for (; t < ntiles; t += gridDim.x) {
         // opaque: LDS addresses and twiddles are recomputed / re-read where they are used instead of being hoisted out of the
@@ -386,38 +362,24 @@ __global__ __launch_bounds__(NT, 1024 / NT) void colz_kernel(ColParams p) {
         // ---- A: straight from the prefetch registers
 #pragma unroll
         for (int u = 0; u < 8; ++u) x[u] = unpack(v[u]);
-        COLZ_ARITH(fwd8<true>(x, a1, a2, a3));
-        if (!(BH_COLZ_PROBE & 2)) {
+        fwd8<true>(x, a1, a2, a3);
 #pragma unroll
-            for (int u = 0; u < 8; ++u) tile[(rowA + 64 * u) * CP + cp] = pack(x[u]);
-        }
-        // this tile's multiplier rows (distribution C) ride behind steps A and B (BH_COLZ_ONEXT: they were requested a tile ago)
-        if (!BH_COLZ_ONEXT) load_otf(base);
-#ifndef BH_COLZ_EARLY
-#define BH_COLZ_EARLY 0  // 1 (real transfer function only: its rows take half the registers): the next tile's rows are requested here,
-                         // behind the whole tile, instead of behind B' and A' — A/B
-#endif
-        constexpr bool EARLY = BH_COLZ_EARLY && MODE == COL_FILTER;
-        if (EARLY && tn < ntiles) load_tile(base_n);
-        COLZ_SYNC();
+        for (int u = 0; u < 8; ++u) tile[(rowA + 64 * u) * CP + cp] = pack(x[u]);
+        // this tile's multiplier rows (distribution C) ride behind steps A and B
+        load_otf(base);
+        __syncthreads();
         // ---- B
         const cf b1 = tb[(go & 7) * 3], b2 = tb[(go & 7) * 3 + 1], b3 = tb[(go & 7) * 3 + 2];
-        if (!(BH_COLZ_PROBE & 2)) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) x[i] = unpack(tile[(rowB + 8 * i) * CP + cp]);
-        }
-        COLZ_ARITH(fwd8<true>(x, b1, b2, b3));
-        if (!(BH_COLZ_PROBE & 2)) {
+        for (int i = 0; i < 8; ++i) x[i] = unpack(tile[(rowB + 8 * i) * CP + cp]);
+        fwd8<true>(x, b1, b2, b3);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) tile[(rowB + 8 * i) * CP + cp] = pack(x[i]);
-        }
-        COLZ_SYNC();
+        for (int i = 0; i < 8; ++i) tile[(rowB + 8 * i) * CP + cp] = pack(x[i]);
+        __syncthreads();
         // ---- C, the spectral product, C'
-        if (!(BH_COLZ_PROBE & 2)) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) x[i] = unpack(tile[(rowC + i) * CP + cp]);
-        }
-        COLZ_ARITH(fwd8<false>(x, a1, a1, a1));
+        for (int i = 0; i < 8; ++i) x[i] = unpack(tile[(rowC + i) * CP + cp]);
+        fwd8<false>(x, a1, a1, a1);
         if (MODE == COL_PCC && p.otf_out && ct * W + 2 * cp < XP) {  // roll: this image is the stored one next time
             const unsigned laneC8 = (unsigned)xw::opaque_i((int)laneC8_);
 #pragma unroll
@@ -425,41 +387,32 @@ __global__ __launch_bounds__(NT, 1024 / NT) void colz_kernel(ColParams p) {
                 *reinterpret_cast<float4*>(reinterpret_cast<unsigned char*>(p.otf_out + scalar_off(base + (long)(8 * GPW * wave + i) * row_stride)) + laneC8) = pack(x[i]);
         }
 #pragma unroll
-        for (int i = 0; i < 8; ++i) COLZ_ARITH(x[i] = spec_mul<MODE>(x[i], o[i], p.pcc_norm | (p.pcc_swap << 8), p.scale));
-        if (BH_COLZ_ONEXT && tn < ntiles) load_otf(base_n);
-        COLZ_ARITH(inv8<false>(x, a1, a1, a1));
-        if (!(BH_COLZ_PROBE & 2)) {
+        for (int i = 0; i < 8; ++i) x[i] = spec_mul<MODE>(x[i], o[i], p.pcc_norm | (p.pcc_swap << 8), p.scale);
+        inv8<false>(x, a1, a1, a1);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) tile[(rowC + i) * CP + cp] = pack(x[i]);
-        }
-        COLZ_SYNC();
+        for (int i = 0; i < 8; ++i) tile[(rowC + i) * CP + cp] = pack(x[i]);
+        __syncthreads();
         // the next tile's rows travel behind B' and A'
-        if (!EARLY && tn < ntiles && !(BH_COLZ_PROBE & 16)) load_tile(base_n);
+        if (tn < ntiles) load_tile(base_n);
         // ---- B'
         {
             const int gq = xw::opaque_i(go) & 7;
             const cf c1 = tb[gq * 3], c2 = tb[gq * 3 + 1], c3 = tb[gq * 3 + 2];
-            if (!(BH_COLZ_PROBE & 2)) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) x[i] = unpack(tile[(rowB + 8 * i) * CP + cp]);
-            }
-            COLZ_ARITH(inv8<true>(x, c1, c2, c3));
+            for (int i = 0; i < 8; ++i) x[i] = unpack(tile[(rowB + 8 * i) * CP + cp]);
+            inv8<true>(x, c1, c2, c3);
         }
-        if (!(BH_COLZ_PROBE & 2)) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) tile[(rowB + 8 * i) * CP + cp] = pack(x[i]);
-        }
-        COLZ_SYNC();
+        for (int i = 0; i < 8; ++i) tile[(rowB + 8 * i) * CP + cp] = pack(x[i]);
+        __syncthreads();
         // ---- A' and out (the same LDS words this thread overwrites in the next tile's A: no barrier in between)
-        if (!(BH_COLZ_PROBE & 2)) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) x[u] = unpack(tile[(rowA + 64 * u) * CP + cp]);
-        }
+        for (int u = 0; u < 8; ++u) x[u] = unpack(tile[(rowA + 64 * u) * CP + cp]);
         {
             const int ga = xw::opaque_i(go);
-            COLZ_ARITH(inv8<true>(x, ta[ga * 3], ta[ga * 3 + 1], ta[ga * 3 + 2]));
+            inv8<true>(x, ta[ga * 3], ta[ga * 3 + 1], ta[ga * 3 + 2]);
         }
-        if (ct * W + 2 * cp < XP && (!(BH_COLZ_PROBE & 16) || p.scale == 12345.678f)) {  // pad columns of a ragged last tile are never stored
+        if (ct * W + 2 * cp < XP) {  // pad columns of a ragged last tile are never stored
             const unsigned la = (unsigned)xw::opaque_i((int)laneA);
 #pragma unroll
             for (int u = 0; u < 8; ++u)

@@ -1,6 +1,6 @@
 // Z pass of 384- and 768-point columns (3 x 128, 3 x 256) with register stages — the deskewed volumes of BASELINE config 4,
 // (342, 1024, 1517), and config 2, (683, 2048, 3034), run Richardson-Lucy at the boxes (384, 1024, 1536) and (768, 2048, 3072).
-// Included by fftconv.hip after fftconv_colz.inc, whose radix-8 butterflies it reuses.
+// Included by fftconv_colreg.hip after fftconv_colz.inc, whose radix-8 butterflies it reuses.
 //
 // col_pass_kernel runs such a column as a radix-3 step, a radix-2 step and three radix-4 steps through LDS, forward and back:
 // ten LDS round trips and eleven barriers per 96-KiB tile (1.89 ms per pass at that box, 3.3 TB/s).  Here, as in colz_kernel,

@@ -1,5 +1,5 @@
 // Radix-3 wave-private X passes of the fused FFT engine: rows of 1536 or 3072 voxels (packed complex transforms of
-// M = 3 L points, L = 256 or 512) — included by fftconv.hip after fftconv_xw.inc, whose helpers it shares.
+// M = 3 L points, L = 256 or 512) — included by fftconv_xw.hip after fftconv_xw.inc, whose helpers it shares.
 //
 // A deskewed volume never has power-of-two rows: the wrap-padded engine box of BASELINE config 4's (342, 1024, 1517) volume is
 // (384, 1024, 1536), that of config 2's (683, 2048, 3034) is (768, 2048, 3072).  Those rows used to take the tile kernels of
@@ -32,7 +32,6 @@ using xw::opaque_i;
 using xw::pack2;
 using xw::Params;
 using xw::parity;
-using xw::xw_div;
 using xw::xw_fence;
 using xw::FUSED_RATIO;
 using xw::FUSED_RATIO_WRAP;
@@ -523,8 +522,8 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
                 for (int i = 0; i < 24; ++i) {
                     float2 v = x[i];
                     if (RATIO) {
-                        v.x = xw_div(aux[i].x, fmaxf(v.x, p.eps));
-                        v.y = xw_div(aux[i].y, fmaxf(v.y, p.eps));
+                        v.x = aux[i].x / fmaxf(v.x, p.eps);
+                        v.y = aux[i].y / fmaxf(v.y, p.eps);
                     } else if (UPDATE) {
                         v.x = fmaxf(aux[i].x * v.x, 0.0f);
                         v.y = fmaxf(aux[i].y * v.y, 0.0f);

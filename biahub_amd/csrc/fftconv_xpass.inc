@@ -1,4 +1,4 @@
-// X passes of the fused FFT engine for tiles of BH_XP_XR rows — included by fftconv.hip once per tile height, inside a
+// X passes of the fused FFT engine for tiles of BH_XP_XR rows — included by fftconv_xtile.hip once per tile height, inside a
 // namespace of its own (xr16: rows up to 2048 voxels; xr8: up to 3072, where 16 rows of LDS no longer fit).
 constexpr int FC_XR = BH_XP_XR;    // rows per X-pass tile (FC_XH row pairs y, y + Y/2); a power of two
 constexpr int FC_XH = FC_XR / 2;
@@ -98,9 +98,9 @@ __device__ __forceinline__ void x_forward_from_lds(cf* buf, const cf* tw, const 
     if (R3) {
         odd_step<false, 1, FC_XNT, RDX>(buf, d.Lm, FC_LOGXR, FC_XPITCH, ut + M, tid);
         __syncthreads();
-        fft_lds<false, 2, 1, FC_XR16, false, FC_XNT>(buf, d.Lm, d.logM, FC_LOGXR, FC_XPITCH, tw, tid, M);
+        fft_lds<false, 2, 1, false, FC_XNT>(buf, d.Lm, d.logM, FC_LOGXR, FC_XPITCH, tw, tid, M);
     } else {
-        fft_lds<false, 2, 1, FC_XR16, false, FC_XNT>(buf, M, d.logM, FC_LOGXR, FC_XPITCH, tw, tid);
+        fft_lds<false, 2, 1, false, FC_XNT>(buf, M, d.logM, FC_LOGXR, FC_XPITCH, tw, tid);
     }
     untangle_lds<false, RDX>(buf, ut, M, tid, d.Lm);
     __syncthreads();
@@ -321,11 +321,11 @@ __global__ __launch_bounds__(FC_XNT) void x_inv_kernel(XParams p) {
         untangle_lds<true, RDX>(buf, ut, M, tid, d.Lm);
         __syncthreads();
         if (R3) {
-            fft_lds<true, 1, 1, FC_XR16, false, FC_XNT>(buf, d.Lm, d.logM, FC_LOGXR, FC_XPITCH, tw, tid, M);
+            fft_lds<true, 1, 1, false, FC_XNT>(buf, d.Lm, d.logM, FC_LOGXR, FC_XPITCH, tw, tid, M);
             odd_step<true, 1, FC_XNT, RDX>(buf, d.Lm, FC_LOGXR, FC_XPITCH, ut + M, tid);
             __syncthreads();
         } else {
-            fft_lds<true, 1, 1, FC_XR16, false, FC_XNT>(buf, M, d.logM, FC_LOGXR, FC_XPITCH, tw, tid);
+            fft_lds<true, 1, 1, false, FC_XNT>(buf, M, d.logM, FC_LOGXR, FC_XPITCH, tw, tid);
         }
         if (!FUSE && EPI != XE_STORE) load_aux();
         // natural order now: z[j] = x[2j] + i x[2j+1]; apply the fused epilogue to the real rows
@@ -388,13 +388,7 @@ static int launch_x(bh_ctx* ctx, const ConvPlan& pl, bool inverse, int epi, cons
     const long ntiles = (long)pl.d.Z * (pl.d.Y / FC_XR);
     const int wgs_per_cu = (int)std::max<size_t>(1, std::min<size_t>(2048 / FC_XNT, (160 * 1024) / (lds + 1024)));
     const int grid = (int)std::min<long>(ntiles, (long)ctx->num_cus * wgs_per_cu);
-    auto run = [&](auto kern) -> int {
-        BH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(FC_XNT), lds, ctx->stream, p);
-        BH_CHECK_HIP(hipGetLastError());
-        return BH_OK;
-    };
+    auto run = [&](auto kern) { return launch_lds(ctx, kern, grid, FC_XNT, lds, p); };
     const int QPR = pl.d.M / 2;
     int rpr = std::max(1, FC_XNT / QPR);
     if (r3) {  // rows per round: the largest power of two that fits (kernel: RPR)

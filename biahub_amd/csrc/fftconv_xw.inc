@@ -1,4 +1,4 @@
-// Wave-private X passes of the fused FFT engine (rows of 1024 or 2048 voxels) — included by fftconv.hip.
+// Wave-private X passes of the fused FFT engine (rows of 1024 or 2048 voxels) — included by fftconv_xw.hip (and by fftconv_colreg.hip for its in-register butterflies).
 //
 // The tile-based X passes (fftconv_xpass.inc) keep 16 rows in one LDS tile and run every radix-4 step as an LDS round trip
 // with a workgroup barrier: 14 round trips per fused pass, LDS- and barrier-bound at 38-50 % of the HBM rate
@@ -18,29 +18,9 @@
 // against numpy's FFT, with the LDS bank conflicts of every exchange priced by the rules of MI355X_MICROARCH.md).
 namespace xw {
 
-// compile-time tuning / probing switches (tools/build_variant.py): defaults are the measured best
-#ifndef BH_XW_FAST_DIV
-#define BH_XW_FAST_DIV 0
-#endif
-#ifndef BH_XW_AUX_EARLY
-#define BH_XW_AUX_EARLY 0
-#endif
-#ifndef BH_XW_PROBE
-#define BH_XW_PROBE 0  // timing probes with WRONG results: bit 0 = no stage arithmetic, bit 1 = no LDS exchanges, bit 2 = no untangle / Y step
-#endif
-
+// (enum Mode and struct Params: fftconv_dev.hpp)
 constexpr int NT = 512;       // 8 wavefronts per workgroup, one workgroup per CU, up to 256 VGPRs per lane
 constexpr int NW = NT / 64;
-
-// the _WRAP modes (fftconv_x3.inc only): Richardson-Lucy at a wrap-padded box without a fold pass — the epilogue's result is
-// wrap-extended along x inside the row and along z by re-reading the source plane, out of place (Params::S_out, Params::wz / wx)
-// INV_UPDATE_CROP: the last update of that loop — max(est * ., 0) stored straight into the UNPADDED output volume (rows of
-// wx.n floats at any 4-byte alignment; planes / columns outside the volume are not stored): no crop pass
-// INV_ARGMAX: the inverse transform is not stored at all — every wavefront keeps the first occurrence of max |.| of the rows it
-// produced and writes one ArgMax to Params::out (an ArgMax[gridDim.x * NW] there): the phase cross-correlation's peak search
-// without the correlation volume ever reaching memory
-enum Mode { FWD = 0, INV_STORE = 1, INV_RATIO = 2, INV_UPDATE = 3, FUSED_RATIO = 4, FUSED_UPDATE = 5, FUSED_RATIO_WRAP = 6, FUSED_UPDATE_WRAP = 7,
-            INV_UPDATE_CROP = 8, INV_ARGMAX = 9 };
 
 template <int LOGM>
 struct Geo {
@@ -60,28 +40,6 @@ struct Geo {
     static constexpr int NTW1 = 7 * BLK, NTW2 = (R2 - 1) * 8, NUT = 8 * LG + 8;
     static constexpr int NTAB = NTW1 + NTW2 + NUT + (NTW2 & 1);  // keeps the row buffers 16-B aligned
     static constexpr size_t LDS_BYTES = ((size_t)NTAB + (size_t)NW * PAIRS * 2 * ROWWORDS) * 8;
-};
-
-struct Params {
-    const float* in;   // FWD: real rows
-    cf* S;             // spectrum rows (pitch XP)
-    float* out;        // FWD: optional max(in, 0) copy; INV_*: real output; FUSED_UPDATE: the estimate; INV_ARGMAX: ArgMax partials
-    const float* aux;  // d (ratio) or est (update)
-    const cf* tab;     // [tw1 | tw2 | ut | ut1] (make_tables)
-    const cf* twy;     // w_Y^y, y < Y/2
-    int Z, Y, XP;
-    float eps;
-    const double* norm_mean;  // FWD only, may be null: transform x / mean - 1 instead of x (inten_normalization_3D fused into the load)
-    double* rowsum;           // INV_UPDATE only, may be null: rowsum[z * Y + y] = sum over x of the row just stored (float64) — what
-                              // the one-pass overhang fill of a deskew that follows needs of this volume (deskew_rows.inc)
-    // _WRAP modes: the spectrum rows are read from S and written to S_out (a second buffer: a margin plane re-reads the plane it
-    // mirrors, which another wavefront is overwriting), and the wrap geometry of the padded axes: the volume's N voxels sit at
-    // box positions [off, off + N); the result is defined on rel = pos - off (pos - off - P when that is >= N + mhi) in
-    // [-mlo, N + mhi) as the value at rel mod N, and is zero elsewhere
-    cf* S_out;
-    struct Wrap {
-        int n, off, mlo, mhi;
-    } wz, wx;
 };
 
 __host__ __device__ constexpr int parity(int v) {
@@ -449,13 +407,11 @@ __host__ __device__ __forceinline__ int off_d3(const LaneAddr& a, int c) {  // 1
 __host__ __device__ __forceinline__ float4 pack2(cf a, cf b) { return make_float4(a.x, a.y, b.x, b.y); }
 template <int LOGM>
 __host__ __device__ __forceinline__ void put_dr(unsigned char* buf, const cf (&x)[16], const LaneAddr& a) {
-    if (BH_XW_PROBE & 2) return;
 #pragma unroll
     for (int r = 0; r < 8; ++r) *reinterpret_cast<float4*>(buf + off_dr<LOGM>(a, r)) = pack2(x[2 * r], x[2 * r + 1]);
 }
 template <int LOGM>
 __host__ __device__ __forceinline__ void get_dr(const unsigned char* buf, cf (&x)[16], const LaneAddr& a) {
-    if (BH_XW_PROBE & 2) return;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const float4 v = *reinterpret_cast<const float4*>(buf + off_dr<LOGM>(a, r));
@@ -465,25 +421,21 @@ __host__ __device__ __forceinline__ void get_dr(const unsigned char* buf, cf (&x
 }
 template <int LOGM>
 __host__ __device__ __forceinline__ void put_d2(unsigned char* buf, const cf (&x)[16], const LaneAddr& a) {
-    if (BH_XW_PROBE & 2) return;
 #pragma unroll
     for (int rho = 0; rho < 16; ++rho) *reinterpret_cast<cf*>(buf + off_d2<LOGM>(a, rho)) = x[rho];
 }
 template <int LOGM>
 __host__ __device__ __forceinline__ void get_d2(const unsigned char* buf, cf (&x)[16], const LaneAddr& a) {
-    if (BH_XW_PROBE & 2) return;
 #pragma unroll
     for (int rho = 0; rho < 16; ++rho) x[rho] = *reinterpret_cast<const cf*>(buf + off_d2<LOGM>(a, rho));
 }
 template <int LOGM>
 __host__ __device__ __forceinline__ void put_d3(unsigned char* buf, const cf (&x)[16], const LaneAddr& a) {
-    if (BH_XW_PROBE & 2) return;
 #pragma unroll
     for (int c = 0; c < 8; ++c) *reinterpret_cast<float4*>(buf + off_d3(a, c)) = pack2(x[2 * c], x[2 * c + 1]);
 }
 template <int LOGM>
 __host__ __device__ __forceinline__ void get_d3(const unsigned char* buf, cf (&x)[16], const LaneAddr& a) {
-    if (BH_XW_PROBE & 2) return;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const float4 v = *reinterpret_cast<const float4*>(buf + off_d3(a, c));
@@ -545,36 +497,36 @@ template <int LOGM>
 __host__ __device__ __forceinline__ void transform_fwd(cf (&xa)[16], cf (&xb)[16], unsigned char* ba, const cf* tw1, const cf* tw2,
                                               int l, const LaneAddr& a) {
     unsigned char* bb = ba + Geo<LOGM>::ROWWORDS * 8;
-    if (!(BH_XW_PROBE & 1)) stage_top1<LOGM, false>(xa, tw1, l);  // row by row: the scheduler would otherwise interleave both rows' butterflies and
+    stage_top1<LOGM, false>(xa, tw1, l);  // row by row: the scheduler would otherwise interleave both rows' butterflies and
     put_dr<LOGM>(ba, xa, a);              // run out of registers next to the prefetched pair
     xw_fence();
-    if (!(BH_XW_PROBE & 1)) stage_top1<LOGM, false>(xb, tw1, l);
+    stage_top1<LOGM, false>(xb, tw1, l);
     put_dr<LOGM>(bb, xb, a);
     xw_fence();
     get_d2<LOGM>(ba, xa, a);
     get_d2<LOGM>(bb, xb, a);
     xw_fence();
-    if (!(BH_XW_PROBE & 1)) stage_mid<LOGM, false>(xa, xb, tw2, l);
+    stage_mid<LOGM, false>(xa, xb, tw2, l);
     put_d2<LOGM>(ba, xa, a);
     put_d2<LOGM>(bb, xb, a);
     xw_fence();
     get_d3<LOGM>(ba, xa, a);
     get_d3<LOGM>(bb, xb, a);
     xw_fence();
-    if (!(BH_XW_PROBE & 1)) stage_low<false>(xa, xb);
+    stage_low<false>(xa, xb);
 }
 template <int LOGM>
 __host__ __device__ __forceinline__ void transform_inv_head(cf (&xa)[16], cf (&xb)[16], unsigned char* ba, const cf* tw2, int l,
                                                    const LaneAddr& a) {
     unsigned char* bb = ba + Geo<LOGM>::ROWWORDS * 8;
-    if (!(BH_XW_PROBE & 1)) stage_low<true>(xa, xb);
+    stage_low<true>(xa, xb);
     put_d3<LOGM>(ba, xa, a);
     put_d3<LOGM>(bb, xb, a);
     xw_fence();
     get_d2<LOGM>(ba, xa, a);
     get_d2<LOGM>(bb, xb, a);
     xw_fence();
-    if (!(BH_XW_PROBE & 1)) stage_mid<LOGM, true>(xa, xb, tw2, l);
+    stage_mid<LOGM, true>(xa, xb, tw2, l);
     put_d2<LOGM>(ba, xa, a);
     put_d2<LOGM>(bb, xb, a);
     xw_fence();
@@ -606,20 +558,16 @@ __host__ __device__ __forceinline__ void pair_inv_head(cf (&xa)[16], cf (&xb)[16
     }
     const cf un = cmulc(nyb, wy);
     float na = nya.x + un.x, nb = nya.x - un.x;
-    if (!(BH_XW_PROBE & 4)) {
-        untangle<LOGM, true>(xa, ut, l, na);
-        untangle<LOGM, true>(xb, ut, l, nb);
-    }
+    untangle<LOGM, true>(xa, ut, l, na);
+    untangle<LOGM, true>(xb, ut, l, nb);
     transform_inv_head<LOGM>(xa, xb, ba, tw2, l, a);
 }
 // forward tail: spectrum-end registers after the forward transform -> untangle, Y step; returns the Nyquist bins of A / B
 template <int LOGM>
 __host__ __device__ __forceinline__ void pair_fwd_tail(cf (&xa)[16], cf (&xb)[16], cf& nyA, cf& nyB, cf wy, const cf* ut, int l) {
     float na = 0.f, nb = 0.f;
-    if (!(BH_XW_PROBE & 4)) {
-        untangle<LOGM, false>(xa, ut, l, na);
-        untangle<LOGM, false>(xb, ut, l, nb);
-    }
+    untangle<LOGM, false>(xa, ut, l, na);
+    untangle<LOGM, false>(xb, ut, l, nb);
     // A = X_a + X_b, B = (X_a - X_b) w_Y^y
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -629,21 +577,6 @@ __host__ __device__ __forceinline__ void pair_fwd_tail(cf (&xa)[16], cf (&xb)[16
     }
     nyA = make_float2(na + nb, 0.f);
     nyB = cmul(make_float2(na - nb, 0.f), wy);
-}
-
-// d / c of the ratio epilogue.  BH_XW_FAST_DIV=1: d * v_rcp_f32(c) (1 ulp reciprocal, ~1.5 ulp quotient) instead of the
-// correctly rounded division (10 instructions); c >= eps > 0 is a normal number either way.
-__device__ __forceinline__ float xw_div(float d, float c) {
-#if BH_XW_FAST_DIV == 2
-    // one Newton step on the quotient: q = d r, q += r (d - c q) — 4 instructions, <= 1 ulp (c >= eps is normal, no scaling needed)
-    const float r = __builtin_amdgcn_rcpf(c);
-    const float q = d * r;
-    return __builtin_fmaf(__builtin_fmaf(-c, q, d), r, q);
-#elif BH_XW_FAST_DIV
-    return d * __builtin_amdgcn_rcpf(c);
-#else
-    return d / c;
-#endif
 }
 
 __device__ __forceinline__ int opaque_i(int v) {
@@ -680,15 +613,8 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
     const LaneAddr a0 = lane_addr<LOGM>(l);
 
     const int Yh = p.Y >> 1, XP = p.XP;
-    const int npairs_all = p.Z * Yh;                // host: < 2^31
-#ifndef BH_XW_CONTIG
-#define BH_XW_CONTIG 0  // 1: a workgroup walks a CONTIGUOUS range of row pairs (its wavefronts interleaved inside it) instead of every grid-th group
-#endif
-    // contiguous: workgroup b owns pairs [b per_wg, (b + 1) per_wg), per_wg a multiple of the pairs one workgroup step covers
-    const int wgstep = NW * G::PAIRS;
-    const int per_wg = ((npairs_all + (int)gridDim.x - 1) / (int)gridDim.x + wgstep - 1) / wgstep * wgstep;
-    const int npairs = BH_XW_CONTIG ? min(npairs_all, ((int)blockIdx.x + 1) * per_wg) : npairs_all;
-    const int pstep = BH_XW_CONTIG ? wgstep : (int)gridDim.x * NW * G::PAIRS;
+    const int npairs = p.Z * Yh;                    // host: < 2^31
+    const int pstep = (int)gridDim.x * NW * G::PAIRS;
     // a wavefront's PAIRS row pairs are neighbours in y (Yh is a multiple of PAIRS): rows ra0 + grp and rb0 + grp
     const int laneS = grp * XP * 8 + l * 16;        // byte offset into a spectrum row pair
     const int laneR = grp * X * 4 + l * 16;         // byte offset into a real row pair
@@ -750,7 +676,7 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
 
     float best_v = -1.0f;  // INV_ARGMAX: this lane's running maximum of |.| and its flat index
     long best_i = 0;
-    int pb = BH_XW_CONTIG ? (int)blockIdx.x * per_wg + wave * G::PAIRS : (blockIdx.x * NW + wave) * G::PAIRS;
+    int pb = (blockIdx.x * NW + wave) * G::PAIRS;
     if (pb < npairs) load_pair(pb);
     for (; pb < npairs; pb += pstep) {
         LaneAddr a = a0;
@@ -774,8 +700,7 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
         if (HAS_INV) {
             const cf nya_cur = nya, nyb_cur = nyb;  // this pair's Nyquist bins: the prefetch below overwrites the carried ones
             if (MODE == INV_STORE || ARGMAX) load_pair(pnext);  // no epilogue operand: the next pair rides behind the whole inverse
-            // this pair's d / est rows ride behind the inverse transform: BH_XW_AUX_EARLY = 0 both rows behind its last stage,
-            // 1 both behind the whole transform, 2 row a behind the whole transform and row b behind the last stage
+            // this pair's d / est rows ride behind the inverse transform, ahead of its last stage
             float4 auxa[8], auxb[8];
             auto load_aux_a = [&]() {
 #pragma unroll
@@ -785,12 +710,11 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r) auxb[r] = *at(p.aux, rw.sb_, X * 4, laneR, r * (G::BLK / 2) * 16);
             };
-            if ((RATIO || UPDATE) && BH_XW_AUX_EARLY >= 1) load_aux_a();
-            if ((RATIO || UPDATE) && BH_XW_AUX_EARLY == 1) load_aux_b();
-            if (BH_XW_AUX_EARLY >= 1) xw_fence();
             pair_inv_head<LOGM>(xa, xb, nya_cur, nyb_cur, wy, ba, tw2, ut, l, a);
-            if ((RATIO || UPDATE) && BH_XW_AUX_EARLY == 0) load_aux_a();
-            if ((RATIO || UPDATE) && BH_XW_AUX_EARLY != 1) load_aux_b();
+            if (RATIO || UPDATE) {
+                load_aux_a();
+                load_aux_b();
+            }
             // last inverse stage and epilogue, one row at a time: row b waits in its LDS buffer while row a's registers and
             // epilogue operands are live (natural order, real-side distribution: registers (2 r, 2 r + 1) = four
             // consecutive reals)
@@ -801,16 +725,16 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                 const long yq = CROP ? row % p.Y + grp : 0;
                 get_dr<LOGM>(buf, x, a);
                 xw_fence();
-                if (!(BH_XW_PROBE & 1)) stage_top1<LOGM, true>(x, tw1, l);
+                stage_top1<LOGM, true>(x, tw1, l);
                 xw_fence();
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     float4 v = pack2(x[2 * r], x[2 * r + 1]);
                     if (RATIO) {
-                        v.x = xw_div(aux[r].x, fmaxf(v.x, p.eps));
-                        v.y = xw_div(aux[r].y, fmaxf(v.y, p.eps));
-                        v.z = xw_div(aux[r].z, fmaxf(v.z, p.eps));
-                        v.w = xw_div(aux[r].w, fmaxf(v.w, p.eps));
+                        v.x = aux[r].x / fmaxf(v.x, p.eps);
+                        v.y = aux[r].y / fmaxf(v.y, p.eps);
+                        v.z = aux[r].z / fmaxf(v.z, p.eps);
+                        v.w = aux[r].w / fmaxf(v.w, p.eps);
                     } else if (UPDATE) {
                         v.x = fmaxf(aux[r].x * v.x, 0.0f);
                         v.y = fmaxf(aux[r].y * v.y, 0.0f);

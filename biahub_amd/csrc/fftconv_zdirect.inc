@@ -1,4 +1,4 @@
-// Z pass of Richardson-Lucy as a direct circular convolution along z with compact taps.  Included by fftconv.hip (namespace bh).
+// Z pass of Richardson-Lucy as a direct circular convolution along z with compact taps.  Included by fftconv_colreg.hip (namespace bh).
 //
 // The Z pass of the engine computes Z-inverse(H . Z-forward(column)) for every (ky, kx) column of the half spectrum, with
 // H = DFT_z(Q) and Q(t; ky, kx) the PSF transformed along x and y only.  A PSF of z-extent K makes Q nonzero for |t| <= K / 2

@@ -14,23 +14,12 @@
 //   compute: phase (weak-object transfer function of a thick 3-D sample) and fluorescence (|PSF|^2 spectrum) transfer
 //            functions from the optical parameters, on hipFFT complex transforms.
 #include "common.hpp"
+#include "fftconv.hpp"
 
 #include <cstring>
 #include <mutex>
 
 namespace bh {
-
-typedef float2 cf;
-
-struct ConvPlan;
-bool fftconv_supported_ex(int64_t Z, int64_t Y, int64_t X, bool radix3);
-int fftconv_plan(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, ConvPlan** out);
-size_t fftconv_spectrum_elems(const ConvPlan& pl);
-int fftconv_stage_inverse_filter(bh_ctx* ctx, const ConvPlan& pl, const void* tf, bool tf_complex, float reg, bool bf16,
-                                 void* filt);
-int fftconv_apply_staged_filter(bh_ctx* ctx, const ConvPlan& pl, const float* in, const void* filt, bool bf16, cf* spec,
-                                float* out, const double* norm_mean);
-bool fftconv_fuses_normalisation(const ConvPlan& pl);
 
 static dim3 grid_for(bh_ctx* ctx, int64_t n, int block = 256) {
     int64_t g = (n + block - 1) / block;
