@@ -863,7 +863,10 @@ def pyramid_cli(input_position_dirpaths, sbatch_filepath, local, levels, method)
 
 def main(argv=None):
     argv = expand_eat_all(list(sys.argv[1:] if argv is None else argv))
-    return cli.main(args=argv, standalone_mode=True)
+    try:
+        return cli.main(args=argv, standalone_mode=True)
+    finally:
+        parallel.shutdown()  # standalone mode leaves through SystemExit: the process group goes before the interpreter does
 
 
 if __name__ == "__main__":

@@ -31,9 +31,11 @@ namespace bh {
 // rows per X-pass tile for a row length: the configured height while its LDS tile fits, 8 rows beyond M = 1024
 static int x_tile_rows(int64_t X) { return X / 2 > 1024 ? 8 : BH_FC_XR; }
 
-// Shapes the engine runs: X a power of two; Y and Z powers of two or — `radix3` — three times one (the column passes then
-// start with a radix-3 step).  Callers whose spectral arithmetic knows the scrambled coefficient order (Tikhonov's filter
-// staging) ask without `radix3`; order-agnostic ones (Richardson-Lucy at a padded box) may ask with it.
+// Shapes the engine runs: every axis a power of two or — `radix3` — three or five times one (rows and columns then start
+// with a radix-3 / radix-5 step).  Every caller asks with `radix3` today: Richardson-Lucy and phase correlation are
+// order-agnostic, and the staging kernels that write a natural-order transfer function into the scrambled coefficient order
+// (tikhonov_filter_rows_kernel, inverse_filter_rows_kernel: bh_tikhonov, bh_inverse_filter) compute the stored position of
+// 3 * 2^k and 5 * 2^k axes too.  Without it (fftconv_supported; BH_FC_NORADIX3 for Richardson-Lucy) only powers of two pass.
 bool fftconv_supported_ex(int64_t Z, int64_t Y, int64_t X, bool radix3) {
     auto pow2 = [](int64_t v) { return v > 0 && (v & (v - 1)) == 0; };
     auto ok = [&](int64_t v) { return pow2(v) || (radix3 && ((v % 3 == 0 && pow2(v / 3)) || (v % 5 == 0 && pow2(v / 5)))); };

@@ -11,6 +11,8 @@ Richardson-Lucy (the project's definition, the C3 comment in ``oracle_np.py``):
     e0   = max(d, 0)
     e   <- max(e * corr_h(d / max(conv_h(e), eps)), 0)        circular convolution / correlation
 Tikhonov (``oracle_np.tikhonov_zyx``):  real(ifftn(fftn(x) * conj(H) / (|H|^2 + reg)))
+Inverse filter (``oracle_np.wo_apply_inverse_transfer_function``):  crop_z(real(ifftn(fftn(pad_z(n(x))) * conj(H) / (|H|^2 + reg))))
+for any H, with n(x) = x / mean(x) - 1; and the same with the filter stored as bfloat16 pairs, rounded as the staging kernel does.
 
 Inputs may be numpy arrays or torch tensors; results are float64 torch tensors on the input's device (or ``device``).
 Nothing here imports the product package.
@@ -112,3 +114,92 @@ def tikhonov_f64(zyx, transfer_function, regularization_strength: float = 1e-3, 
     H = H.to(torch.complex128) if H.is_complex() else H.to(F64)
     filt = H.conj() / (H.abs() ** 2 + float(regularization_strength))
     return torch.fft.ifftn(torch.fft.fftn(x) * filt).real.contiguous()
+
+
+# ----------------------------------------------------------------------------- the inverse filter (apply-inv-tf)
+def normalize_pad_f64(zyx, z_padding: int = 0, normalize: bool = False, device=None, mirror: bool = True) -> torch.Tensor:
+    """pad_z(n(x)) in float64: n(x) = x / mean(x) - 1 when ``normalize``; ``z_padding`` planes on either side of z, as
+    ``oracle_np.wo_apply_inverse_transfer_function`` defines them — the volume's own edge planes mirrored (plane pad - 1 - z
+    below, plane Z - 1 - k for the k-th plane above) when ``z_padding < Z``, zeros otherwise (or when ``mirror`` is off)."""
+    x = _tensor(zyx, device, F64)
+    if normalize:
+        x = x / x.mean() - 1.0
+    pad = int(z_padding)
+    if not pad:
+        return x
+    Z = x.shape[0]
+    xp = torch.zeros((Z + 2 * pad,) + tuple(x.shape[1:]), dtype=F64, device=x.device)
+    xp[pad:pad + Z] = x
+    if mirror and pad < Z:
+        xp[:pad] = x[:pad].flip(0)
+        xp[pad + Z:] = x[Z - pad:].flip(0)
+    return xp
+
+
+def _apply_filter_f64(xp: torch.Tensor, filt: torch.Tensor, z_padding: int) -> torch.Tensor:
+    out = torch.fft.ifftn(torch.fft.fftn(xp) * filt).real
+    pad = int(z_padding)
+    return (out[pad:out.shape[0] - pad] if pad else out).contiguous()
+
+
+def inverse_filter_f64(zyx, transfer_function, z_padding: int = 0, regularization_strength: float = 1e-3,
+                       normalize: bool = False, device=None, mirror: bool = True) -> torch.Tensor:
+    """crop_z(Re ifftn(fftn(pad_z(n(x))) * conj(H) / (|H|^2 + reg))) on full complex128 spectra; H of the padded shape in natural
+    FFT order, real or complex, with or without any symmetry (the real part keeps only the filter's Hermitian part)."""
+    xp = normalize_pad_f64(zyx, z_padding, normalize, device, mirror)
+    H = _tensor(transfer_function, xp.device)
+    if tuple(H.shape) != tuple(xp.shape):
+        raise ValueError(f"transfer function shape {tuple(H.shape)} != padded data shape {tuple(xp.shape)}")
+    H = H.to(torch.complex128) if H.is_complex() else H.to(F64)
+    return _apply_filter_f64(xp, H.conj() / (H.abs() ** 2 + float(regularization_strength)), z_padding)
+
+
+def minus_k(H: torch.Tensor) -> torch.Tensor:
+    """H(-k): every axis reversed about bin 0 (bin 0 and, on even axes, the Nyquist bin map to themselves)."""
+    dims = tuple(range(H.ndim))
+    return torch.roll(H.flip(dims), (1,) * H.ndim, dims)
+
+
+def staged_filter_f32(transfer_function, regularization_strength: float, scale: float, one_division: bool = False):
+    """The value ``inverse_filter_rows_kernel`` (csrc/fftconv.hip) stages per bin, formed in float32 from a complex64 / float32
+    H on the full spectrum:  F_h(k) * scale,  F_h(k) = (conj(H(k)) q(k) + H(-k) q(-k)) / 2,  q = 1 / (|H|^2 + reg) — the
+    Hermitian part of conj(H) / (|H|^2 + reg), which is all that acts on a real volume.  Returns (re, im) float32.
+    ``one_division``: the same value with h / (|h|^2 + reg) as one division instead of reciprocal-then-multiply (a second
+    float32 formulation; the distance between the two is the float32 uncertainty of the staged value)."""
+    H = _tensor(transfer_function)
+    H = H.to(torch.complex64) if H.is_complex() else H.to(torch.float32)
+    hr, hi = (H.real, H.imag) if H.is_complex() else (H, torch.zeros_like(H))
+    reg = torch.tensor(float(regularization_strength), dtype=torch.float32, device=H.device)
+    s = torch.tensor(float(scale), dtype=torch.float32, device=H.device)
+    den = hr * hr + hi * hi + reg
+    if one_division:
+        fr, fi = hr / den, hi / den
+    else:
+        q = 1.0 / den
+        fr, fi = hr * q, hi * q
+    return 0.5 * (fr + minus_k(fr)) * s, 0.5 * (-fi + minus_k(fi)) * s
+
+
+def bf16_round(t: torch.Tensor, truncate: bool = False) -> torch.Tensor:
+    """float32 -> bfloat16 -> float32: round to nearest even (``truncate``: drop the low 16 bits instead — a planted defect)."""
+    if truncate:
+        return (t.contiguous().view(torch.int32) & -65536).view(torch.float32)
+    return t.to(torch.bfloat16).to(torch.float32)
+
+
+def inverse_filter_bf16_f64(zyx, transfer_function, z_padding: int = 0, regularization_strength: float = 1e-3,
+                            normalize: bool = False, device=None, mirror: bool = True, truncate: bool = False,
+                            one_division: bool = False) -> torch.Tensor:
+    """The inverse filter with the staged filter kept as bfloat16 pairs, transforms in float64.  The staged value is what the
+    kernel documents: F_h(k) formed in float32, multiplied by float32(2 / V) (V the padded volume's voxel count — what the
+    engine's unnormalised transforms need), THEN each component rounded to bfloat16 (round to nearest even) and widened; the
+    2 / V is divided back out in float64.  The scale belongs inside the rounding: V is no power of two on 3 * 2^k and
+    5 * 2^k boxes, so rounding F_h itself lands on other bfloat16 values."""
+    xp = normalize_pad_f64(zyx, z_padding, normalize, device, mirror)
+    H = _tensor(transfer_function, xp.device)
+    if tuple(H.shape) != tuple(xp.shape):
+        raise ValueError(f"transfer function shape {tuple(H.shape)} != padded data shape {tuple(xp.shape)}")
+    scale = 2.0 / float(xp.numel())
+    fr, fi = staged_filter_f32(H, regularization_strength, scale, one_division)
+    filt = torch.complex(bf16_round(fr, truncate).to(F64), bf16_round(fi, truncate).to(F64)) / scale
+    return _apply_filter_f64(xp, filt, z_padding)

@@ -15,7 +15,9 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT, rel_err
+from fft_metrics import INVTF_BF16_RMS_TOL, INVTF_BF16_VOXEL_TOL, INVTF_VOXEL_TOL, RMS_TOL, assert_fft_close
 from oracle import oracle_np as O
+from oracle import reference_f64 as R64
 
 pytestmark = pytest.mark.gpu
 
@@ -1884,7 +1886,10 @@ def test_apply_inverse_transfer_function_vs_oracle(gpu, shape, pad):
 
     if pad == 0 and shape[2] >= 64 and shape in ((16, 32, 64), (8, 64, 1024)):
         g16 = apply_inverse_transfer_function_zyx(vol, Hr, pad, 1e-3, False, filter_storage="bf16").cpu().numpy()
-        assert 1e-7 < rel_err(g16, want) <= 1e-2
+        assert 1e-7 < rel_err(g16, want) <= 1e-2   # bfloat16 was used ...
+        # ... and rounded as the kernel documents (a truncating conversion passes the line above: tests/test_invtf_reference.py)
+        assert_fft_close(g16, R64.inverse_filter_bf16_f64(vol, Hr, pad, 1e-3, False), INVTF_BF16_RMS_TOL, INVTF_BF16_VOXEL_TOL,
+                         f"bfloat16 filter {shape}")
     elif shape == (15, 21, 25):
         with pytest.raises(ValueError, match="bfloat16"):
             apply_inverse_transfer_function_zyx(vol, Hr, pad, 1e-3, False, filter_storage="bf16")
@@ -2095,6 +2100,12 @@ def test_radix8_z_pass(gpu, shape, pshape, monkeypatch):
     assert rel_err(new["rl_real"], O.richardson_lucy_zyx(vol, sym, iterations=3, eps=1e-6)) <= FFT_TOL
     assert rel_err(new["rl_complex"], O.richardson_lucy_zyx(vol, asym, iterations=3, eps=1e-6)) <= FFT_TOL
     assert rel_err(new["tikhonov"], O.deconvolve_czyx(vol[None], compute_tranfser_function(sym, shape), 1e-2)[0]) <= FFT_TOL
+    # the inverse filter of both kernels against float64, per voxel: both read the same staged filter, so new-vs-old cannot
+    # see a staging error
+    ref32, ref16 = R64.inverse_filter_f64(v, tfc, 0, 1e-2, False), R64.inverse_filter_bf16_f64(v, tfc, 0, 1e-2, False)
+    for out in (new, old):
+        assert_fft_close(out["inv_f32"], ref32, RMS_TOL, INVTF_VOXEL_TOL, f"inverse filter, float32, {shape}")
+        assert_fft_close(out["inv_bf16"], ref16, INVTF_BF16_RMS_TOL, INVTF_BF16_VOXEL_TOL, f"inverse filter, bfloat16, {shape}")
     assert rel_err(new["pcc_magnitude"], O.phase_cross_corr(vol, mov, "magnitude")[1]) <= 1e-3
 
 
