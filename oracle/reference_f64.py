@@ -13,6 +13,8 @@ Richardson-Lucy (the project's definition, the C3 comment in ``oracle_np.py``):
 Tikhonov (``oracle_np.tikhonov_zyx``):  real(ifftn(fftn(x) * conj(H) / (|H|^2 + reg)))
 Inverse filter (``oracle_np.wo_apply_inverse_transfer_function``):  crop_z(real(ifftn(fftn(pad_z(n(x))) * conj(H) / (|H|^2 + reg))))
 for any H, with n(x) = x / mean(x) - 1; and the same with the filter stored as bfloat16 pairs, rounded as the staging kernel does.
+Phase cross-correlation (``oracle_np.phase_cross_corr``):  |irfftn(F1 conj(F2) / norm)|, fftshifted, and the signed position of its
+first maximum; norm = 1, max(|F1 conj(F2)|, eps) or |F1| |F2|.
 
 Inputs may be numpy arrays or torch tensors; results are float64 torch tensors on the input's device (or ``device``).
 Nothing here imports the product package.
@@ -203,3 +205,47 @@ def inverse_filter_bf16_f64(zyx, transfer_function, z_padding: int = 0, regulari
     fr, fi = staged_filter_f32(H, regularization_strength, scale, one_division)
     filt = torch.complex(bf16_round(fr, truncate).to(F64), bf16_round(fi, truncate).to(F64)) / scale
     return _apply_filter_f64(xp, filt, z_padding)
+
+
+# ----------------------------------------------------------------------------- phase cross-correlation
+PCC_EPS = 1.1920929e-07   # the operator's constant (np.finfo(complex64).eps), whatever the working precision
+
+
+def rfftn_by_axis(x: torch.Tensor) -> torch.Tensor:
+    """rfftn of a 3-D tensor, one axis per call.  The same transform; the CPU back-end of torch 2.10.0 (threaded pocketfft)
+    corrupts the heap in a multi-axis transform over the leading axes of a half spectrum (a loop of rfftn / irfftn at e.g.
+    (4, 512, 33) ends in a segmentation fault), one axis at a time it does not.  With a torch that no longer does, these two
+    helpers can give way to rfftn / irfftn."""
+    return torch.fft.fft(torch.fft.fft(torch.fft.rfft(x, dim=2), dim=1), dim=0)
+
+
+def irfftn_by_axis(spec: torch.Tensor) -> torch.Tensor:
+    """irfftn WITHOUT a shape, one axis per call (see ``rfftn_by_axis``): the last axis comes back with 2 (m - 1) columns."""
+    return torch.fft.irfft(torch.fft.ifft(torch.fft.ifft(spec, dim=0), dim=1), dim=2)
+
+
+def phase_cross_corr_f64(ref, mov, normalization=None, device=None):
+    """``oracle_np.phase_cross_corr`` in float64 / complex128: ``(shift, corr_shifted)``.  corr = irfftn(F1 conj(F2) / norm)
+    WITHOUT a shape, so an odd last axis comes back one shorter; norm is 1 (``None``), max(|F1 conj(F2)|, eps) (``"magnitude"``)
+    or |F1| |F2| (``"classic"``; a zero bin gives NaN, as it does in the definition).  ``corr_shifted`` = fftshift(|corr|), a
+    float64 tensor; ``shift`` a float64 numpy array, the first occurrence of the maximum of |corr| with every component
+    greater than fix(n / 2) wrapped negative."""
+    a, b = _tensor(ref, device, F64), _tensor(mov, device, F64)
+    if a.ndim != 3 or a.shape != b.shape:
+        raise ValueError(f"expected two 3-D images of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    F1, F2 = rfftn_by_axis(a), rfftn_by_axis(b)
+    prod = F1 * F2.conj()
+    if normalization == "magnitude":
+        prod = prod / prod.abs().clamp(min=PCC_EPS)
+    elif normalization == "classic":
+        prod = prod / (F1.abs() * F2.abs())
+    elif normalization is not None:
+        raise ValueError(f"unknown normalization {normalization!r}")
+    del F1, F2
+    mag = irfftn_by_axis(prod).abs_()
+    first = int(torch.argmax(mag))   # the first of equal maxima (a NaN counts as one, as in numpy)
+    shift = np.array(np.unravel_index(first, tuple(mag.shape)), dtype=np.float64)
+    n = np.array(mag.shape, dtype=np.float64)
+    wrap = shift > np.fix(n / 2)
+    shift[wrap] -= n[wrap]
+    return shift, torch.fft.fftshift(mag)

@@ -46,6 +46,54 @@ INVTF_VOXEL_TOL = 6e-3
 INVTF_BF16_RMS_TOL = 2.2e-4
 INVTF_BF16_VOXEL_TOL = 6.3e-2
 
+# Phase cross-correlation (bh_phase_cross_corr*; tests/test_gpu_pcc_f64.py): fftshift(|corr|) against phase_cross_corr_f64.
+# Same rule: 10x the error of the complex64 restatement (tests/pcc_cases.py: phase_cross_corr_c64) against float64, measured on
+# the CPU at every input of the GPU tests (pcc_cases.cpu_inputs: 24 shapes, three shifts each, the roll chains, beads, impulses;
+# tests/test_pcc_reference.py holds the restatement to a tenth of these bounds), never from the engine's output.  By class:
+#   None, camera pairs with their offset: the DC term sits under every voxel.  Restatement rms_rel 8.4e-8 .. 2.3e-7, voxel_rel
+#       3.3e-7 .. 7.2e-7: RMS_TOL and VOXEL_TOL stand.
+#   None about zero (mean-removed pairs, 65535-count beads and impulses on a zero background): rms_rel 1.7e-7 .. 3.0e-7:
+#       RMS_TOL stands.  voxel_rel is max error / (0.01 rms) off the peak, and float32 carries the peak's own rounding, 6e-8 of
+#       its height, along the three axis lines through it, where the volume is ordinary noise a thousand times smaller:
+#       2e-5 .. 1.9e-3 on camera pairs, 1.4e-3 beads, 3.4e-3 two impulses at (12, 32, 500).  10x, rounded up.
+#   magnitude and classic (the two agree to the digits given): every bin has unit weight, so each carries its own relative
+#       rounding, the weak ones most: rms_rel 8.2e-7 .. 2.6e-6 (worst (24, 96, 192), no shift), voxel_rel 2.2e-4 .. 5.5e-3
+#       (worst (1024, 32, 64), third link of the roll chain; the same axis lines); impulses 1.8e-7 / 2.1e-3.  10x, rounded up.
+#   the uniform random volumes of test_gpu_parity.py's three phase cross-correlation tests (pcc_cases.parity_inputs: white, a
+#       mean of 1/2): None 8e-8 .. 2.8e-7 / 3.5e-7 .. 8.3e-7: RMS_TOL and VOXEL_TOL stand.  Normalised, a white spectrum has
+#       nothing but weak bins to weigh: rms_rel 3.7e-7 .. 4.2e-6 (worst (40, 160, 320)), a bound of its own; voxel_rel up to
+#       4.4e-3: PCC_NORM_VOXEL_TOL stands.
+PCC_NONE_VOXEL_TOL = 4e-2
+PCC_NORM_RMS_TOL = 3e-5
+PCC_NORM_VOXEL_TOL = 6e-2
+PCC_NORM_RMS_TOL_WHITE = 5e-5
+
+
+# (rms, voxel) by class — the four derivations above, in their order
+PCC_BOUNDS = {
+    "none_offset": (RMS_TOL, VOXEL_TOL),
+    "none_zero_mean": (RMS_TOL, PCC_NONE_VOXEL_TOL),
+    "normalised": (PCC_NORM_RMS_TOL, PCC_NORM_VOXEL_TOL),
+    "normalised_white": (PCC_NORM_RMS_TOL_WHITE, PCC_NORM_VOXEL_TOL),
+}
+
+
+def pcc_class(normalization, mean_removed=False, white=False):
+    """The class of ``PCC_BOUNDS`` a phase cross-correlation volume belongs to.  Only two of the three arguments matter to any
+    one class: without normalisation, whether the images carry an offset (``mean_removed`` False; the white volumes, whose mean
+    is 1/2, among them, so ``white`` changes nothing there) or stand about zero (mean removed, or beads or impulses on a zero
+    background); normalised, whether the images are camera-like or ``white`` (the uniform random volumes of
+    test_gpu_parity.py) — the normalisation divides any offset out with every other amplitude, so ``mean_removed`` changes
+    nothing there."""
+    if normalization is None:
+        return "none_zero_mean" if mean_removed else "none_offset"
+    return "normalised_white" if white else "normalised"
+
+
+def pcc_bounds(normalization, mean_removed=False, white=False):
+    """(rms, voxel) bounds of a phase cross-correlation volume: ``PCC_BOUNDS[pcc_class(...)]``."""
+    return PCC_BOUNDS[pcc_class(normalization, mean_removed, white)]
+
 
 SLAB_VOXELS = 1 << 24   # planes are taken in slabs of at most this many voxels (at least one plane)
 

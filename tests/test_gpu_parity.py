@@ -15,7 +15,8 @@ import pytest
 import torch
 
 from conftest import GOLDEN, ROOT, rel_err
-from fft_metrics import INVTF_BF16_RMS_TOL, INVTF_BF16_VOXEL_TOL, INVTF_VOXEL_TOL, RMS_TOL, assert_fft_close
+from fft_metrics import INVTF_BF16_RMS_TOL, INVTF_BF16_VOXEL_TOL, INVTF_VOXEL_TOL, RMS_TOL, assert_fft_close, fft_errors, pcc_bounds
+import pcc_cases as P
 from oracle import oracle_np as O
 from oracle import reference_f64 as R64
 
@@ -1069,8 +1070,21 @@ def test_richardson_lucy_properties_large_awkward(gpu, monkeypatch):
     assert float((est - est_ref).abs().max()) <= FFT_TOL * float(est_ref.abs().max())
 
 
+def _pcc_vs_float64(corr, ref_img, mov_img, norm, what, shift=None):
+    """A correlation volume of these tests (uniform random images: pcc_cases.parity_inputs) against the float64 reference, per
+    voxel (bounds: fft_metrics.pcc_bounds, derived on the CPU in tests/test_pcc_reference.py); and the shift, where given."""
+    a, b = (torch.as_tensor(x).cuda() for x in (ref_img, mov_img))
+    want_shift, want = R64.phase_cross_corr_f64(a, b, norm)
+    errs = fft_errors(corr, want)
+    print(f"F64 pcc white {what} {norm}: rms_rel {errs[0]:.2e} voxel_rel {errs[1]:.2e} maxnorm {errs[2]:.2e}")
+    assert_fft_close(corr, want, *pcc_bounds(norm, white=True), f"{what} {norm}")
+    if shift is not None:
+        assert np.array_equal(shift, want_shift), (what, norm, shift, want_shift)
+
+
 def test_phase_cross_corr_golden_and_oracle(gpu):
-    """estimate_stabilization.phase_cross_corr: shifts exact, correlation volume within FFT tolerance."""
+    """estimate_stabilization.phase_cross_corr: shifts exact, correlation volume within FFT tolerance — and, per voxel, within
+    the float32 bounds of the float64 reference."""
     from biahub_amd.estimate_stabilization import phase_cross_corr
 
     z = np.load(GOLDEN / "phase_cross_corr.npz")
@@ -1079,33 +1093,26 @@ def test_phase_cross_corr_golden_and_oracle(gpu):
             sh, corr = phase_cross_corr(z[f"ref{j}"], z[f"mov{j}"], normalization=norm)
             assert sh.dtype == np.float32 and np.array_equal(sh, z[f"shift{j}_{norm}"]), (j, norm, sh)
             assert rel_err(corr, z[f"corr{j}_{norm}"]) <= FFT_TOL, (j, norm)
+            _pcc_vs_float64(corr, z[f"ref{j}"], z[f"mov{j}"], norm, f"golden {j}", sh)
     rng = np.random.default_rng(1)
-    ref = rng.random((32, 48, 40), dtype=np.float32)
+    ref = P.parity_library_volume(rng)
     for roll in ((0, 0, 0), (15, -23, 19), (-16, 24, -20)):
         mov = np.roll(ref, roll, axis=(0, 1, 2))
         want, _ = O.phase_cross_corr(ref, mov, "magnitude")
         got, corr = phase_cross_corr(ref, mov, normalization="magnitude")
+        # the shift and the volume's shape only: normalised without noise the correlation is one spike on a background of pure
+        # rounding, a form pcc_bounds derives no bound for here (test_gpu_pcc_f64.py holds it to float64 in its impulse cases)
         assert np.array_equal(got, want) and corr.shape == ref.shape
-    # power-of-two volumes run on the fused FFT engine (scrambled half-spectrum), everything else on hipFFT: same answers
-    big = rng.random((32, 64, 128), dtype=np.float32)
-    for roll in ((0, 0, 0), (5, -20, 33), (-16, 32, -64)):
-        mov = np.roll(big, roll, axis=(0, 1, 2)) + 0.05 * rng.random(big.shape, dtype=np.float32)
+    # power-of-two volumes run on the fused FFT engine (scrambled half-spectrum), everything else on hipFFT: same answers;
+    # z / y of 3 * 2^k (5 * 2^k): the engine's column passes start with a radix-3 (radix-5) step; the coefficient order changes,
+    # the answers do not
+    for shape, roll, big, mov in P.parity_oracle_pairs(rng):
         for norm in (None, "magnitude", "classic"):
             want, wcorr = O.phase_cross_corr(big, mov, norm)
             got, corr = phase_cross_corr(big, mov, normalization=norm)
-            assert np.array_equal(got, want), (roll, norm, got, want)
-            assert rel_err(corr, wcorr) <= FFT_TOL, (roll, norm)
-    # z / y of 3 * 2^k: the engine's column passes start with a radix-3 step; the coefficient order changes, the answers do not
-    for shape3, rolls in (((48, 96, 64), ((0, 0, 0), (7, -40, 21), (-24, 48, -32))), ((16, 32, 192), ((3, -9, 77), (-8, 16, -96))),
-                          ((40, 160, 320), ((-20, 80, 160), (9, -70, 33)))):
-        r3 = rng.random(shape3, dtype=np.float32)
-        for roll in rolls:
-            mov = np.roll(r3, roll, axis=(0, 1, 2)) + 0.05 * rng.random(r3.shape, dtype=np.float32)
-            for norm in (None, "magnitude", "classic"):
-                want, wcorr = O.phase_cross_corr(r3, mov, norm)
-                got, corr = phase_cross_corr(r3, mov, normalization=norm)
-                assert np.array_equal(got, want), (roll, norm, got, want)
-                assert rel_err(corr, wcorr) <= FFT_TOL, (roll, norm)
+            assert np.array_equal(got, want), (shape, roll, norm, got, want)
+            assert rel_err(corr, wcorr) <= FFT_TOL, (shape, roll, norm)
+            _pcc_vs_float64(corr, big, mov, norm, f"{shape} {roll}", got)
     with pytest.raises(ValueError):
         phase_cross_corr(ref, ref[:-1], normalization=None)
     with pytest.raises(ValueError):
@@ -1116,22 +1123,20 @@ def test_phase_cross_corr_golden_and_oracle(gpu):
 def test_phase_cross_corr_peak_only(gpu):
     """``want_corr=False`` on rows the wave-private X kernels take: the last inverse pass keeps the argmax candidates itself
     (xw::INV_ARGMAX) and the correlation volume is never stored — same shift as the search over the stored volume and as the
-    oracle, including a tie between two equal peaks (np.argmax: the first one) and more row pairs than one launch round."""
+    oracle (the float64 reference on the GPU where the volume is large for the host: (256, 128, 512), stored volume too),
+    including a tie between two equal peaks (np.argmax: the first one) and more row pairs than one launch round."""
     from biahub_amd.estimate_stabilization import phase_cross_corr_device
 
-    rng = np.random.default_rng(21)
-    for shape, rolls in (((16, 32, 512), ((0, 0, 0), (5, -11, 200), (-8, 16, -256))), ((8, 16, 1024), ((3, 7, -500),)),
-                         ((4, 16, 2048), ((-2, 8, 1023),)), ((256, 128, 512), ((100, -50, 17),))):
-        ref = rng.random(shape, dtype=np.float32)
-        for roll in rolls:
-            mov = np.roll(ref, roll, axis=(0, 1, 2)) + 0.05 * rng.random(shape, dtype=np.float32)
-            for norm in (None, "magnitude", "classic"):
-                stored, _ = phase_cross_corr_device(ref, mov, norm, want_corr=True)
-                peak, corr = phase_cross_corr_device(ref, mov, norm, want_corr=False)
-                assert corr is None and np.array_equal(peak, stored), (shape, roll, norm, peak, stored)
-                if shape[0] <= 16:
-                    want, _ = O.phase_cross_corr(ref, mov, norm)
-                    assert np.array_equal(peak, want), (shape, roll, norm, peak, want)
+    for shape, roll, ref, mov in P.parity_peak_only_pairs():
+        for norm in (None, "magnitude", "classic"):
+            stored, volume = phase_cross_corr_device(ref, mov, norm, want_corr=True)
+            peak, corr = phase_cross_corr_device(ref, mov, norm, want_corr=False)
+            assert corr is None and np.array_equal(peak, stored), (shape, roll, norm, peak, stored)
+            if shape[0] <= 16:
+                want, _ = O.phase_cross_corr(ref, mov, norm)
+                assert np.array_equal(peak, want), (shape, roll, norm, peak, want)
+            else:
+                _pcc_vs_float64(volume, ref, mov, norm, f"{shape} {roll}", peak)
     # two peaks of one height: the correlation of an impulse with two impulses
     ref = np.zeros((8, 16, 512), np.float32)
     mov = np.zeros_like(ref)
@@ -1151,11 +1156,7 @@ def test_prepared_phase_cross_corr(gpu):
     and LDS-stepped Z passes, a 3 * 2^k axis) and on the library path (odd X included)."""
     from biahub_amd.estimate_stabilization import PreparedPhaseCrossCorr, phase_cross_corr_device
 
-    rng = np.random.default_rng(33)
-    for shape in ((16, 32, 512), (32, 64, 128), (512, 16, 64), (48, 32, 64), (20, 30, 50), (9, 14, 31)):
-        vols = [rng.random(shape, dtype=np.float32) for _ in range(2)]
-        vols.append(np.roll(vols[0], (3, -5, 7), axis=(0, 1, 2)) + 0.05 * rng.random(shape, dtype=np.float32))
-        vols.append(np.roll(vols[2], (-2, 4, 9), axis=(0, 1, 2)))
+    for shape, vols in P.parity_prepared_volumes():
         for norm in (None, "magnitude", "classic"):
             for second in (False, True):
                 with PreparedPhaseCrossCorr(vols[0], fixed_is_second=second, device=gpu) as h:
@@ -1167,6 +1168,7 @@ def test_prepared_phase_cross_corr(gpu):
                             assert np.array_equal(got_s, want_s), (shape, norm, second, want_corr, got_s, want_s)
                             if want_corr:
                                 assert rel_err(got_c.cpu().numpy(), want_c.cpu().numpy()) <= 1e-6, (shape, norm, second)
+                                _pcc_vs_float64(got_c, *pair, norm, f"handle {shape} second {second}")
                 # the "previous timepoint" chain: each image against the one before it
                 with PreparedPhaseCrossCorr(vols[0], fixed_is_second=second, device=gpu) as h:
                     for k in range(1, len(vols)):
@@ -1176,6 +1178,7 @@ def test_prepared_phase_cross_corr(gpu):
                         assert np.array_equal(got_s, want_s), (shape, norm, second, k, got_s, want_s)
                         if got_c is not None:
                             assert rel_err(got_c.cpu().numpy(), want_c.cpu().numpy()) <= 1e-6, (shape, norm, second, k)
+                            _pcc_vs_float64(got_c, *pair, norm, f"handle {shape} second {second} roll {k}")
     with PreparedPhaseCrossCorr(vols[0], device=gpu) as h:
         with pytest.raises(ValueError):
             h(vols[0][:-1])
