@@ -15,6 +15,8 @@ Inverse filter (``oracle_np.wo_apply_inverse_transfer_function``):  crop_z(real(
 for any H, with n(x) = x / mean(x) - 1; and the same with the filter stored as bfloat16 pairs, rounded as the staging kernel does.
 Phase cross-correlation (``oracle_np.phase_cross_corr``):  |irfftn(F1 conj(F2) / norm)|, fftshifted, and the signed position of its
 first maximum; norm = 1, max(|F1 conj(F2)|, eps) or |F1| |F2|.
+Smooth + shrink (``oracle_np.smooth_shrink``):  per axis out[i] = sum_k w[k] in[clamp(f i + o + k - R)], the weights rounded to
+float32 as ``bh_smooth_shrink`` stages them, every sum in float64.
 
 Inputs may be numpy arrays or torch tensors; results are float64 torch tensors on the input's device (or ``device``).
 Nothing here imports the product package.
@@ -249,3 +251,32 @@ def phase_cross_corr_f64(ref, mov, normalization=None, device=None):
     wrap = shift > np.fix(n / 2)
     shift[wrap] -= n[wrap]
     return shift, torch.fft.fftshift(mag)
+
+
+# ----------------------------------------------------------------------------- smooth + shrink (registration pyramid)
+def smooth_shrink_f64(vol, sigma, factor):
+    """``oracle_np.smooth_shrink`` with float64 sums: x, then y, then z; per axis No = max(1, N // f) outputs at
+    f i + o, o = ((N - 1) - f (No - 1)) // 2, an edge-clamped sampled Gaussian of radius R = ceil(4 sigma) (R = 0: the identity).
+    The weights are the operator's own constants — exp(-k^2 / (2 sigma^2)) normalised in float64, THEN rounded to float32, as
+    the kernel receives them — so they enter as given; products and sums are float64.  Returns (float64 tensor, offsets)."""
+    out = np.asarray(vol.cpu() if isinstance(vol, torch.Tensor) else vol, dtype=np.float64)
+    if out.ndim != 3:
+        raise ValueError(f"expected a 3-D volume, got {out.shape}")
+    offsets = [0, 0, 0]
+    for a in (2, 1, 0):
+        N, f, s = out.shape[a], int(factor[a]), float(sigma[a])
+        if f < 1 or s < 0.0:
+            raise ValueError("shrink factor must be >= 1 and sigma >= 0")
+        No = max(1, N // f)
+        o = ((N - 1) - f * (No - 1)) // 2
+        offsets[a] = o
+        R = int(np.ceil(4.0 * s))
+        k = np.arange(-R, R + 1)
+        w = np.exp(-0.5 * k.astype(np.float64) ** 2 / (s * s)) if R else np.ones(1)
+        w = (w / w.sum()).astype(np.float32).astype(np.float64)
+        centres = f * np.arange(No) + o
+        acc = np.zeros(out.shape[:a] + (No,) + out.shape[a + 1:], dtype=np.float64)
+        for kk, wk in zip(k, w):
+            acc += wk * np.take(out, np.clip(centres + kk, 0, N - 1), axis=a)
+        out = acc
+    return torch.from_numpy(out), tuple(offsets)
