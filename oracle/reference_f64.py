@@ -17,6 +17,8 @@ Phase cross-correlation (``oracle_np.phase_cross_corr``):  |irfftn(F1 conj(F2) /
 first maximum; norm = 1, max(|F1 conj(F2)|, eps) or |F1| |F2|.
 Smooth + shrink (``oracle_np.smooth_shrink``):  per axis out[i] = sum_k w[k] in[clamp(f i + o + k - R)], the weights rounded to
 float32 as ``bh_smooth_shrink`` stages them, every sum in float64.
+Deskew (``oracle_np.fast_deskew_zyx``):  (1/N) sum_k (v0 w0 + v1 w1) at the float32 sample positions of ``oracle_np.deskew_coords``
+with their float32 weights, every tap, product and sum in float64, and the magnitude sum beside it; then the reference's fill.
 
 Inputs may be numpy arrays or torch tensors; results are float64 torch tensors on the input's device (or ``device``).
 Nothing here imports the product package.
@@ -280,3 +282,70 @@ def smooth_shrink_f64(vol, sigma, factor):
             acc += wk * np.take(out, np.clip(centres + kk, 0, N - 1), axis=a)
         out = acc
     return torch.from_numpy(out), tuple(offsets)
+
+
+# ----------------------------------------------------------------------------- deskew
+def dilate_mask(mask: torch.Tensor, iterations: int = 3) -> torch.Tensor:
+    """``oracle_np.dilate_zero_mask`` on a torch bool tensor (any device): ``iterations`` 3x3x3 dilations, nothing entering from
+    outside the array.  Separable: one or-of-neighbours per axis and iteration."""
+    m = mask.clone()
+    for _ in range(int(iterations)):
+        for axis in range(3):
+            lo, hi = m.narrow(axis, 0, m.shape[axis] - 1), m.narrow(axis, 1, m.shape[axis] - 1)
+            grown = m.clone()
+            grown.narrow(axis, 1, m.shape[axis] - 1).logical_or_(lo)
+            grown.narrow(axis, 0, m.shape[axis] - 1).logical_or_(hi)
+            m = grown
+    return m
+
+
+def deskew_f64(raw, ls_angle_deg, px_to_scan_ratio, keep_overhang, average_n_slices=1, overhang_fill=0, device=None):
+    """``oracle_np.fast_deskew_zyx`` with float64 arithmetic at the float32 sample positions.  The positions are the contract
+    (``oracle_np.deskew_coords``: the reference's float32 operation order, which the kernels reproduce bit for bit), and so are
+    the float32 weights w1 = ix - floor(ix), w0 = (floor(ix) + 1) - ix; the taps (zero outside the scanned range), the products,
+    the sum over the N averaged slices and the division by N are float64.  Integer input is widened exactly.
+
+    Returns ``(V, M, mask, fill)``:
+      V     the deskewed volume before the fill, float64 ``(ceil(Y / N), X, Xp)``;
+      M     (1/N) sum_k (|v0| w0 + |v1| w1), the magnitude a float32 evaluation's rounding error scales with (M == 0: every tap
+            outside the scanned range or zero, V is an exact zero in any precision);
+      mask  with a fill (``keep_overhang`` and ``overhang_fill`` "mean" or non-zero): V == 0 dilated three times by 3x3x3, else None;
+      fill  the float64 mean of V outside ``mask`` (NaN when nothing is outside) or the constant as a float, else None.
+    The filled volume is ``torch.where(mask, fill, V)``."""
+    from . import oracle_np as O
+
+    x = _tensor(raw, device)
+    if x.ndim != 3:
+        raise ValueError(f"raw must be 3-D (Z, Y, X), got {tuple(x.shape)}")
+    Z, Y, X = (int(s) for s in x.shape)
+    N = int(average_n_slices)
+    (_, _, Xp), _ = O.get_deskewed_data_shape((Z, Y, X), ls_angle_deg, px_to_scan_ratio, keep_overhang)
+    Za = -(-Y // N)
+    V = torch.zeros((Za, X, Xp), dtype=F64, device=x.device)
+    M = torch.zeros_like(V)
+    for a in range(Za):
+        for k in range(N):
+            zo = a * N + k
+            plane = x[:, Y - 1 - min(zo, Y - 1), :].to(F64).flip(1)            # (Z, X'), the output's y' axis
+            ix = O.deskew_coords(Z, Y, Xp, ls_angle_deg, px_to_scan_ratio, zo)  # float32
+            fl = np.floor(ix)
+            w1 = (ix - fl).astype(np.float32)
+            w0 = ((fl + np.float32(1.0)) - ix).astype(np.float32)
+            i0 = fl.astype(np.int64)
+            for i, w in ((i0, w0), (i0 + 1, w1)):
+                inside = torch.from_numpy(((i >= 0) & (i < Z)).astype(np.float64) * w.astype(np.float64)).to(x.device)
+                tap = plane[torch.from_numpy(np.clip(i, 0, Z - 1)).to(x.device)].T  # (X', Xp)
+                V[a] += tap * inside
+                M[a] += tap.abs() * inside
+    if N > 1:
+        V /= N
+        M /= N
+    if not (keep_overhang and (overhang_fill == "mean" or overhang_fill != 0)):
+        return V, M, None, None
+    mask = dilate_mask(V == 0, 3)
+    if overhang_fill == "mean":
+        valid = V[~mask]
+        fill = float(valid.mean()) if valid.numel() else float("nan")
+    else:
+        fill = float(overhang_fill)
+    return V, M, mask, fill
