@@ -63,6 +63,7 @@ SIGNATURES = {
     "bh_deskew_rows": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _f64, _f64, _int, _int, _int, _f32, _vp,
                               C.POINTER(_f32), _vp]),
     "bh_deskew_fill_path": (_int, [_vp, C.POINTER(_int)]),
+    "bh_affine_path": (_int, [_vp, C.POINTER(_int)]),
     "bh_overhang_fill": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _f32, _int, C.POINTER(_f32)]),
     "bh_overhang_fill_connectivity": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _f32, _int, _int, C.POINTER(_f32)]),
     "bh_transfer_function": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),

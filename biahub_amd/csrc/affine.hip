@@ -98,6 +98,26 @@ __device__ __forceinline__ float lerp8(f2 P0, f2 P1, f2 P2, f2 P3, unsigned qz, 
     return lerp8f(P0, P1, P2, P3, fzy.x, fzy.y, (float)qx * 2.3283064365386963e-10f);
 }
 
+// lerp8 on np.nan_to_num'd taps, for every site that blends cleaned taps.  Cleaning sends +-inf to +-FLT_MAX, so the difference
+// of two cleaned taps can overflow where the blend itself — a convex combination — is finite (a +inf and a -inf among the
+// eight taps of one voxel: inf, or NaN at a fraction of 0).  Only then, in a cold branch, the blend is redone on the taps
+// scaled by 1/4 (a power of two: exact for every tap above 2^-124, and a tap below that is nothing beside the 2^127 that made the
+// difference overflow) and scaled back, clamped to the range of float32 like the cleaned taps themselves.  Finite blends keep
+// their bits; all sites share this helper, so the kernels stay bit-identical to each other.
+__device__ __forceinline__ float lerp8f_clean(f2 P0, f2 P1, f2 P2, f2 P3, float fzf, float fyf, float fx) {
+    float r = lerp8f(P0, P1, P2, P3, fzf, fyf, fx);
+    if (__builtin_expect(!__builtin_isfinite(r), 0)) {
+        r = lerp8f(P0 * 0.25f, P1 * 0.25f, P2 * 0.25f, P3 * 0.25f, fzf, fyf, fx);
+        // +-FLT_MAX / 4 = +-(2^126 - 2^102): the quarter blend can round up to 2^126, four times which is no float32
+        r = fminf(fmaxf(r, -8.5070586659632215e37f), 8.5070586659632215e37f) * 4.0f;
+    }
+    return r;
+}
+__device__ __forceinline__ float lerp8_clean(f2 P0, f2 P1, f2 P2, f2 P3, unsigned qz, unsigned qy, unsigned qx) {
+    const f2 fzy = f2{(float)qz, (float)qy} * 2.3283064365386963e-10f;  // the fractions as lerp8 widens them
+    return lerp8f_clean(P0, P1, P2, P3, fzy.x, fzy.y, (float)qx * 2.3283064365386963e-10f);
+}
+
 constexpr int A_NW = 4, A_NT = 64 * A_NW;  // waves / threads per workgroup
 
 struct TileBox {  // per-tile source box, written by threads 0..2, read by everyone after a barrier
@@ -326,8 +346,8 @@ __device__ __forceinline__ void sample_tile(const TIN* __restrict__ in, float* _
                     const f2 P3 = {((const float*)t11)[0], ((const float*)t11)[1]};
                     float r = lerp8(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
                     if (__builtin_expect(!__builtin_isfinite(r), 0))  // a NaN / inf tap: redo on np.nan_to_num'd taps
-                        r = lerp8(clean2(P0), clean2(P1), clean2(P2), clean2(P3), (unsigned)c0[0], (unsigned)c0[1],
-                                  (unsigned)c0[2]);
+                        r = lerp8_clean(clean2(P0), clean2(P1), clean2(P2), clean2(P3), (unsigned)c0[0], (unsigned)c0[1],
+                                        (unsigned)c0[2]);
                     o[k * ostep + ox] = r;
 #pragma unroll
                     for (int a = 0; a < 3; ++a) c0[a] += p.mq[4 * a];
@@ -377,7 +397,7 @@ __device__ __forceinline__ void sample_tile(const TIN* __restrict__ in, float* _
                     const f2 P1 = {fetch(z0, y1, x0), fetch(z0, y1, x1)};
                     const f2 P2 = {fetch(z1, y0, x0), fetch(z1, y0, x1)};
                     const f2 P3 = {fetch(z1, y1, x0), fetch(z1, y1, x1)};
-                    r = lerp8(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
+                    r = lerp8_clean(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
                 }
                 o[k * ostep] = r;
 #pragma unroll
@@ -593,7 +613,7 @@ __global__ __launch_bounds__(256) void affine_gather_kernel(const TIN* __restric
                 const f2 P1 = {fetch(z0, y1, x0), fetch(z0, y1, x1)};
                 const f2 P2 = {fetch(z1, y0, x0), fetch(z1, y0, x1)};
                 const f2 P3 = {fetch(z1, y1, x0), fetch(z1, y1, x1)};
-                r = lerp8(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
+                r = lerp8_clean(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
             }
             out[((size_t)oz * p.Yo + oy) * p.Xo + ox] = r;
 #pragma unroll
@@ -752,6 +772,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
                          int64_t Yo, int64_t Xo, const int64_t crop_lo[3]) {
     using namespace bh;
     BH_REQUIRE(ctx && in && out && matrix, "NULL argument");
+    ctx->affine_path = -1;  // a call that is refused below launched nothing
     BH_REQUIRE(Zi > 0 && Yi > 0 && Xi > 0 && Zo > 0 && Yo > 0 && Xo > 0, "invalid shape");
     BH_REQUIRE(Zi < (1ll << 30) && Yi < (1ll << 30) && Xi < (1ll << 30) && Zo < (1ll << 30) && Yo < (1ll << 30) &&
                    Xo < (1ll << 30),
@@ -765,6 +786,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
     BH_CHECK_HIP(hipSetDevice(ctx->device));
     if (interpolation == BH_INTERP_CUBIC) {
         for (int i = 0; i < 12; ++i) BH_REQUIRE(std::fabs(matrix[i]) < 1073741824.0, "matrix entry %d out of range", i);
+        ctx->affine_path = 4;
         ScopedTimer timer(ctx, T_AFFINE);
         return affine_cubic(ctx, in, in_dtype, Zi, Yi, Xi, matrix, cval, out, Zo, Yo, Xo, crop_lo);
     }
@@ -825,6 +847,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
     }
     ScopedTimer timer(ctx, T_AFFINE);
     if (zw::takes(p)) {  // z-separable linear warp: wave-private z walk (affine_zwalk.inc)
+        ctx->affine_path = 2;
         switch (in_dtype) {
             case BH_DT_F32: return zw::launch(ctx, (const float*)in, out, p);
             case BH_DT_U16: return zw::launch(ctx, (const uint16_t*)in, out, p);
@@ -837,6 +860,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
         // weak z coupling: the z walk with per-lane source planes (affine_zoblique.inc)
         int64_t zchunk = 0;
         const int slot = zo::plan(p, &zchunk);
+        if (slot) ctx->affine_path = 3;
         if (slot && in_dtype == BH_DT_F32) return zo::launch(ctx, (const float*)in, out, p, slot, zchunk);
         if (slot && in_dtype == BH_DT_U16) return zo::launch(ctx, (const uint16_t*)in, out, p, slot, zchunk);
         if (slot) return zo::launch(ctx, (const int16_t*)in, out, p, slot, zchunk);
@@ -844,6 +868,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
     // a full tile's source box does not fit LDS: compact blocks gathering through the caches (BH_AFFINE_GATHER=0, and
     // BH_AFFINE_NOZWALK=1 — "everything on the tile kernel", the reference of the bit-identity tests —: the tile kernel)
     if (!box_fits && !(getenv("BH_AFFINE_GATHER") && atoi(getenv("BH_AFFINE_GATHER")) == 0) && getenv("BH_AFFINE_NOZWALK") == nullptr) {
+        ctx->affine_path = 1;
         switch (in_dtype) {
             case BH_DT_F32: return launch_affine_gather(ctx, (const float*)in, out, p);
             case BH_DT_U16: return launch_affine_gather(ctx, (const uint16_t*)in, out, p);
@@ -852,6 +877,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
             default: BH_REQUIRE(false, "unsupported input dtype code %d", in_dtype);
         }
     }
+    ctx->affine_path = 0;
     switch (in_dtype) {
         case BH_DT_F32: return launch_affine(ctx, (const float*)in, out, p);
         case BH_DT_U16: return launch_affine(ctx, (const uint16_t*)in, out, p);
@@ -859,5 +885,11 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
         case BH_DT_I16: return launch_affine(ctx, (const int16_t*)in, out, p);
         default: BH_REQUIRE(false, "unsupported input dtype code %d", in_dtype);
     }
+    return BH_OK;
+}
+
+extern "C" int bh_affine_path(bh_ctx* ctx, int* path) {
+    BH_REQUIRE(ctx != nullptr && path != nullptr, "NULL argument");
+    *path = ctx->affine_path;
     return BH_OK;
 }

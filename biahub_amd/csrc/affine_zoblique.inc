@@ -50,7 +50,7 @@ __device__ __forceinline__ float slow_voxel(const TIN* __restrict__ in, const Af
     const f2 P1 = {fetch(z0, y1, x0), fetch(z0, y1, x1)};
     const f2 P2 = {fetch(z1, y0, x0), fetch(z1, y0, x1)};
     const f2 P3 = {fetch(z1, y1, x0), fetch(z1, y1, x1)};
-    return lerp8(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
+    return lerp8_clean(P0, P1, P2, P3, (unsigned)c0[0], (unsigned)c0[1], (unsigned)c0[2]);
 }
 
 template <typename TIN, int BOUNDARY>
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void zo
                 const f2 P2 = zw::lds_pair<TIN>(s1, off), P3 = zw::lds_pair<TIN>(s1, off + pitch);
                 float v = lerp8(P0, P1, P2, P3, (unsigned)c[r][0], (unsigned)c[r][1], (unsigned)c[r][2]);
                 if (__builtin_expect(!__builtin_isfinite(v), 0))  // a NaN / inf tap: redo on np.nan_to_num'd taps
-                    v = lerp8(clean2(P0), clean2(P1), clean2(P2), clean2(P3), (unsigned)c[r][0], (unsigned)c[r][1], (unsigned)c[r][2]);
+                    v = lerp8_clean(clean2(P0), clean2(P1), clean2(P2), clean2(P3), (unsigned)c[r][0], (unsigned)c[r][1], (unsigned)c[r][2]);
                 if (store[r]) (oplane + (size_t)r * p.Xo)[ox] = v;
             }
         } else {

@@ -380,7 +380,7 @@ __device__ __forceinline__ void walk(const TIN* __restrict__ in, float* __restri
                     const f2 P1 = clean2(fix_pair<XEDGE>(load_pair<TIN>(pl0, R.off1[r]), R.sel[r]));
                     const f2 P2 = clean2(fix_pair<XEDGE>(load_pair<TIN>(pl1, R.off0[r]), R.sel[r]));
                     const f2 P3 = clean2(fix_pair<XEDGE>(load_pair<TIN>(pl1, R.off1[r]), R.sel[r]));
-                    v[r] = lerp8f(P0, P1, P2, P3, fzf, R.fy[r], R.fx[r]);
+                    v[r] = lerp8f_clean(P0, P1, P2, P3, fzf, R.fy[r], R.fx[r]);
                 }
             }
         }

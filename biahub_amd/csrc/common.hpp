@@ -90,6 +90,7 @@ struct bh_ctx {
     std::map<std::string, bh::Scratch> scratch;
     int num_cus = 256;
     int deskew_path = 0;     // how the last bh_deskew filled the overhang: 0 mask pipeline (or no fill), 1 one-pass (deskew_rows.inc)
+    int affine_path = -1;    // the launch of the last bh_affine: 0 staged tiles, 1 compact blocks, 2 z walk, 3 oblique walk, 4 cubic
     int plans_replaced = 0;  // 3-D library plans that failed their self-check and were rebuilt decomposed (context.hip)
     // Richardson-Lucy OTF cache: the OTF in "fc_otf" belongs to the PSF kept in "rl_psf_kept" (compared byte for byte on every
     // call; the hash is informational) / these shapes / this spectrum layout

@@ -94,6 +94,16 @@ def affine_device(vol, matrix, output_shape_zyx, interpolation="linear", boundar
     return out
 
 
+def affine_path(device=None) -> int:
+    """Which launch the last ``affine_device`` on ``device`` chose (diagnostic): 0 staged tiles, 1 compact blocks, 2 z walk,
+    3 oblique walk, 4 cubic B-spline; -1 before the first warp and after one that was refused."""
+    dev = resolve_device(device if device is not None else "cuda")
+    ctx = get_context(dev)
+    path = C.c_int(-1)
+    _lib.check(ctx.lib.bh_affine_path(ctx.handle, C.byref(path)))
+    return int(path.value)
+
+
 def cast_like_scipy(t: torch.Tensor, dtype) -> torch.Tensor:
     """SciPy's conversion of an interpolated value into the output dtype (ni_interpolation.c, CASE_INTERP_OUT_*): floating
     types are cast; integers round half away from zero (unsigned: negatives -> 0) and saturate at the type's range."""

@@ -436,6 +436,9 @@ int bh_average_patches(bh_ctx* ctx, const float* in, int64_t Z, int64_t Y, int64
 int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, int64_t Yi, int64_t Xi,
               const double matrix[12], int interpolation, int boundary, float cval, float* out,
               int64_t Zo, int64_t Yo, int64_t Xo, const int64_t crop_lo[3]);
+/* Diagnostic (host only, does not synchronise): the launch the last bh_affine of this context chose — 0 staged tiles,
+ * 1 compact blocks, 2 z walk, 3 oblique walk, 4 cubic B-spline; -1 before the first call and after a call that was refused. */
+int bh_affine_path(bh_ctx* ctx, int* path);
 
 /* Cubic B-spline coefficients of a volume (the prefilter of scipy.ndimage.affine_transform(order=3, mode="constant"):
  * biahub/core/transform.py:374-396, biahub/register.py:271-272): per axis the recursive inverse of the sampled cubic

@@ -19,6 +19,9 @@ Smooth + shrink (``oracle_np.smooth_shrink``):  per axis out[i] = sum_k w[k] in[
 float32 as ``bh_smooth_shrink`` stages them, every sum in float64.
 Deskew (``oracle_np.fast_deskew_zyx``):  (1/N) sum_k (v0 w0 + v1 w1) at the float32 sample positions of ``oracle_np.deskew_coords``
 with their float32 weights, every tap, product and sum in float64, and the magnitude sum beside it; then the reference's fill.
+Affine warp (``oracle_np.affine_pull``, orders 0 and 1):  the inside rule on the float64 coordinate; linear with an edge clamp at
+the operator's Q32.32 sample positions (exact integers), every tap, weight and sum in float64; ZEROS and nearest at the float64
+positions; and the largest tap magnitude beside it.
 
 Inputs may be numpy arrays or torch tensors; results are float64 torch tensors on the input's device (or ``device``).
 Nothing here imports the product package.
@@ -349,3 +352,101 @@ def deskew_f64(raw, ls_angle_deg, px_to_scan_ratio, keep_overhang, average_n_sli
     else:
         fill = float(overhang_fill)
     return V, M, mask, fill
+
+
+# ----------------------------------------------------------------------------- affine warp
+def llround_q32(matrix) -> np.ndarray:
+    """``llround(m * 2^32)`` of every entry as int64: round half AWAY from zero (C's llround; ``np.rint`` rounds half to even).
+    ``m * 2^32`` is exact in float64 (a power of two), so is floor(|.| + 0.5) below 2^52; entries are below 2^30 in magnitude."""
+    m = np.asarray(matrix, dtype=np.float64) * 4294967296.0
+    if not (np.abs(m) < 2.0 ** 62).all():
+        raise ValueError("matrix entry out of the Q32.32 range")
+    a = np.abs(m)
+    fl = np.floor(a)
+    r = np.where(a - fl >= 0.5, fl + 1.0, fl)      # a - fl is exact
+    return (np.sign(m) * r).astype(np.int64)
+
+
+def warp_f64(vol, matrix, output_shape, crop_lo=(0, 0, 0), interpolation="linear", boundary=0, cval=0.0, device=None):
+    """``out(p) = in(M p)`` for p = crop_lo + (z, y, x) over ``output_shape``, in float64: the pull-resample of ``oracle_np.affine_pull``
+    (orders 0 and 1; boundary 0 ITK, 1 SciPy "constant", 2 zeros / grid-constant) as the operator defines it.
+
+    * The input is cleaned first (``nan_to_num(nan=0)`` in its own type: NaN -> 0, +-inf -> +-FLT_MAX), then widened exactly.
+    * ``inside`` is decided on the float64 coordinate in numpy's association, ((m0 z + m1 y) + m2 x) + m3, by affine_pull's rule
+      per boundary (ZEROS: everywhere); outside it V is ``cval`` (rounded to float32 once, as the operator receives it).
+    * Linear with ITK / SCIPY_CONSTANT: the sample position is the Q32.32 coordinate cq = mq0 z + mq1 y + mq2 x + mq3 in exact
+      int64 arithmetic, mq = llround(m 2^32): taps at cq >> 32 and + 1 clamped to the volume, fractions (cq & 0xffffffff) / 2^32
+      (exact in float64), the trilinear blend in float64.  The position grid is part of the operator.
+    * Linear with ZEROS, and nearest: float64 positions, floor(c) / floor(c + 0.5), as affine_pull.
+
+    Returns ``(V, M, inside)``: V float64; M the largest |tap| among the (clamped, cleaned) taps of the voxel — with ZEROS also
+    |cval| —, the scale a float32 evaluation's rounding error is measured in (``cval``'s magnitude outside); inside bool."""
+    if isinstance(vol, np.ndarray) and not vol.flags.writeable:
+        vol = vol.copy()        # torch does not wrap read-only arrays quietly
+    x = _tensor(vol, device)
+    if x.ndim != 3:
+        raise ValueError(f"vol must be 3-D (Z, Y, X), got {tuple(x.shape)}")
+    if interpolation not in ("linear", "nearestneighbor"):
+        raise ValueError(f"unknown interpolation {interpolation!r}")
+    dev = x.device
+    if x.dtype == torch.uint16:
+        x = x.to(torch.int32)
+    if x.is_floating_point():
+        x = torch.nan_to_num(x, nan=0.0)
+    x = x.to(F64)
+    dims = tuple(int(n) for n in x.shape)
+    m = np.asarray(matrix, dtype=np.float64)[:3, :4]
+    cv = float(np.float32(cval))
+    grids = [torch.arange(int(lo), int(lo) + int(n), device=dev, dtype=torch.int64) for lo, n in zip(crop_lo, output_shape)]
+    gz, gy, gx = grids[0][:, None, None], grids[1][None, :, None], grids[2][None, None, :]
+    fz, fy, fx = gz.to(F64), gy.to(F64), gx.to(F64)
+    c = [((float(m[a, 0]) * fz + float(m[a, 1]) * fy) + float(m[a, 2]) * fx) + float(m[a, 3]) for a in range(3)]
+    inside = torch.ones(tuple(int(n) for n in output_shape), dtype=torch.bool, device=dev)
+    for ca, n in zip(c, dims):
+        if boundary == 0:
+            inside &= (ca >= -0.5) & (ca < n - 0.5)
+        elif boundary == 1:
+            inside &= (ca >= 0.0) & (ca <= n - 1)
+    flat = x.reshape(-1)
+
+    def tap(iz, iy, ix):
+        return flat[(iz.clamp(0, dims[0] - 1) * dims[1] + iy.clamp(0, dims[1] - 1)) * dims[2] + ix.clamp(0, dims[2] - 1)]
+
+    cvt = torch.full((), cv, dtype=F64, device=dev)
+    if interpolation == "nearestneighbor":
+        idx = [torch.floor(ca + 0.5).to(torch.int64) for ca in c]
+        val = tap(*idx)
+        if boundary != 0:
+            ok = torch.ones_like(inside)
+            for i, n in zip(idx, dims):
+                ok &= (i >= 0) & (i < n)
+            val = torch.where(ok, val, cvt)
+        V = torch.where(inside, val, cvt)
+        return V, V.abs(), inside
+    if boundary == 2:
+        base = [torch.floor(ca) for ca in c]
+        frac = [ca - b for ca, b in zip(c, base)]
+        base = [b.to(torch.int64) for b in base]
+    else:
+        mq = llround_q32(m)
+        cq = [(int(mq[a, 0]) * gz + int(mq[a, 1]) * gy) + int(mq[a, 2]) * gx + int(mq[a, 3]) for a in range(3)]
+        base = [q >> 32 for q in cq]
+        frac = [(q & 0xFFFFFFFF).to(F64) / 4294967296.0 for q in cq]
+    V = torch.zeros(inside.shape, dtype=F64, device=dev)
+    M = torch.zeros_like(V)
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                w = (frac[0] if dz else 1 - frac[0]) * (frac[1] if dy else 1 - frac[1]) * (frac[2] if dx else 1 - frac[2])
+                iz, iy, ix = base[0] + dz, base[1] + dy, base[2] + dx
+                v = tap(iz, iy, ix)
+                if boundary == 2:
+                    ok = (iz >= 0) & (iz < dims[0]) & (iy >= 0) & (iy < dims[1]) & (ix >= 0) & (ix < dims[2])
+                    v = torch.where(ok, v, cvt)
+                V += w * v
+                M = torch.maximum(M, v.abs())
+    if boundary == 2:
+        M = torch.maximum(M, cvt.abs())
+    V = torch.where(inside, V, cvt)
+    M = torch.where(inside, M, cvt.abs())
+    return V, M, inside
