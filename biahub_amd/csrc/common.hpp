@@ -92,13 +92,11 @@ struct bh_ctx {
     int deskew_path = 0;     // how the last bh_deskew filled the overhang: 0 mask pipeline (or no fill), 1 one-pass (deskew_rows.inc)
     int affine_path = -1;    // the launch of the last bh_affine: 0 staged tiles, 1 compact blocks, 2 z walk, 3 oblique walk, 4 cubic
     int plans_replaced = 0;  // 3-D library plans that failed their self-check and were rebuilt decomposed (context.hip)
-    // Richardson-Lucy OTF cache: the OTF in "fc_otf" belongs to the PSF kept in "rl_psf_kept" (compared byte for byte on every
-    // call; the hash is informational) / these shapes / this spectrum layout
-    bool otf_valid = false;
-    unsigned long long otf_hash = 0;
-    int otf_tag = 0;  // spectrum layout of the plan that built it (fftconv_plan_tag)
+    // One-shot Richardson-Lucy on the engine box: the handle of the last call, its transfer function in scratch "fc_otf" /
+    // "fc_otf_real" (not owned), built from the PSF kept in "rl_psf_kept" (compared byte for byte on every call).  Whoever
+    // overwrites or frees that scratch calls rl_oneshot_drop first.
+    bh_rl* rl_oneshot = nullptr;
     void* spec_tuned = nullptr;  // the "fc_spec" allocation fftconv_tune_spectrum chose (or accepted) for this context
-    int64_t otf_dims[6] = {0, 0, 0, 0, 0, 0};
 };
 
 namespace bh {
@@ -133,6 +131,27 @@ struct ScopedTimer {
         }
     }
 };
+
+// One iteration's share of the span it lives through, into ms_override[slot] (read back by bh_last_elapsed_ms): the slot's
+// own event pair, so nothing to create, destroy or leak on an error path.  With timing off, or nothing to iterate, it does
+// nothing; with timing on its end waits for the stream.
+struct ScopedIterTimer {
+    bh_ctx* ctx;
+    int slot, n;
+    ScopedIterTimer(bh_ctx* c, int s, int iterations) : ctx(c), slot(s), n(c->timing ? iterations : 0) {
+        if (n > 0) (void)hipEventRecord(ctx->ev[2 * slot], ctx->stream);
+    }
+    ~ScopedIterTimer() {
+        float ms = 0;
+        if (n > 0 && hipEventRecord(ctx->ev[2 * slot + 1], ctx->stream) == hipSuccess &&
+            hipEventSynchronize(ctx->ev[2 * slot + 1]) == hipSuccess &&
+            hipEventElapsedTime(&ms, ctx->ev[2 * slot], ctx->ev[2 * slot + 1]) == hipSuccess)
+            ctx->ms_override[slot] = ms / n;
+    }
+};
+
+// forgets the one-shot Richardson-Lucy handle of the context (deconv.hip): its transfer function's scratch is about to change
+void rl_oneshot_drop(bh_ctx* ctx);
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -486,10 +486,10 @@ int bh_ctx_release_workspace(bh_ctx* ctx) {
         if (kv.second.work) (void)bh::dev_free(kv.second.work);
     }
     ctx->plans.clear();
+    bh::rl_oneshot_drop(ctx);
     for (auto& kv : ctx->scratch)
         if (kv.second.ptr) (void)bh::dev_free(kv.second.ptr);
     ctx->scratch.clear();
-    ctx->otf_valid = false;
     ctx->spec_tuned = nullptr;
     return BH_OK;
 }

@@ -13,6 +13,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace bh {
 
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(256) void fold_update_kernel(const float* __restric
     }
 }
 
-// ---- wrap-padding for Richardson-Lucy on the fused engine at a power-of-two box (richardson_lucy_engine_padded) ----
+// ---- wrap-padding for Richardson-Lucy on the fused engine at a power-of-two box (rl_padded_run) ----
 // dst voxel t (box D) takes src voxel soff + wrap_N(t - doff) when t - doff lies within [-lo, N - 1 + hi] on every axis,
 // else 0.  With an N-pitched source this builds the wrap-padded box; with a box-pitched source it re-wraps the margins
 // from the interior; with D = N it crops.
@@ -502,7 +503,8 @@ static int stage_rl_psf(bh_ctx* ctx, const float* psf, int64_t pz, int64_t py, i
 
 // The iterations of Richardson-Lucy on the fused engine with the transfer function in hand (`otf`: NS complex, or NS floats
 // when `otf_real`; with zr >= 0 the compact z taps of that radius instead): spectrum scratch (auditioned once per allocation),
-// optional event timing, no host synchronisation otherwise.  Shared by the one-shot entry and the prepared handle.
+// optional event timing, no host synchronisation otherwise.  Per iteration two 5-pass convolutions; the divide and the
+// multiply / clip ride in the inverse X passes.
 static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, int iterations, float eps,
                          float* out) {
     const size_t NS = fftconv_spectrum_elems(*pl);
@@ -517,93 +519,31 @@ static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
         ctx->spec_tuned = spec;
         BH_TRY(tune_rc);
     }
-    hipStream_t s = ctx->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->timing) {
-        BH_CHECK_HIP(hipEventCreate(&e0));
-        BH_CHECK_HIP(hipEventCreate(&e1));
-        BH_CHECK_HIP(hipEventRecord(e0, s));
-    }
-    BH_TRY(fftconv_richardson_lucy(ctx, *pl, d, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, iterations, eps, out));
-    if (e0) {
-        BH_CHECK_HIP(hipEventRecord(e1, s));
-        BH_CHECK_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        BH_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ctx->ms_override[T_RL_ITER] = ms / iterations;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    return BH_OK;
+    ScopedIterTimer iter_timer(ctx, T_RL_ITER, iterations);
+    return fftconv_richardson_lucy(ctx, *pl, d, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, iterations, eps, out);
 }
 
-// Richardson-Lucy on the fused engine: per iteration two 5-pass convolutions, the divide and the
-// multiply/clip ride in the inverse X passes.  One-shot form: the transfer function is cached in the context and validated
-// against the PSF's bytes on every call (one small kernel, a 24-byte read-back and a stream synchronisation);
-// bh_richardson_lucy_create / _apply is the form without that per-call stall.
-static int richardson_lucy_fused(bh_ctx* ctx, const float* d, const float* psf, int64_t pz, int64_t py, int64_t px,
-                                 int64_t Z, int64_t Y, int64_t X, int iterations, float eps, float* out) {
-    const int64_t V = Z * Y * X;
-    if (iterations == 0) {  // e0 = max(d, 0): nothing to convolve (the fused passes write `out` only from iteration 1 on)
-        hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, ctx->stream, d, out, V);
-        BH_CHECK_HIP(hipGetLastError());
-        return BH_OK;
-    }
-    ConvPlan* pl;
-    BH_TRY(fftconv_plan(ctx, Z, Y, X, &pl));
-    const size_t NS = fftconv_spectrum_elems(*pl);
-    float* real = nullptr;
-    cf* otf;
+// One read of the PSF on the device (one small kernel, a 24-byte read-back and a stream synchronisation) answers two things.
+// `same`: it equals `kept`, the device copy of the PSF a kept transfer function was built from, word for word.  (A pointer
+// match would not do instead: the adapters upload the PSF anew for every call, and a buffer that kept its address may have
+// changed its contents.)
+// `real_form`: THE symmetry decision.  A PSF with odd extents that equals its point mirror bit for bit (every theoretical PSF;
+// the bench's Gaussian) sits symmetric about the origin after staging, so its transfer function is REAL: the imaginary parts
+// the transforms leave are round-off.  The Z passes then read one float per bin instead of two (17.4 -> 8.7 GB per iteration
+// at config 2) and convolution and correlation are the same pass.  BH_RL_COMPLEX_OTF=1 keeps the general path (A/B switch).
+static int rl_probe_psf(bh_ctx* ctx, const float* psf, const int64_t K[3], const uint32_t* kept, bool* same, bool* real_form) {
     double* psum;
-    BH_TRY(get_scratch(ctx, "fc_otf", NS * sizeof(cf), (void**)&otf));
     BH_TRY(get_scratch(ctx, "rl_psum", 64, (void**)&psum));
-    hipStream_t s = ctx->stream;
-    ScopedTimer timer(ctx, T_RL_TOTAL);
-    // The OTF only depends on the PSF and the shapes: a plate reuses one PSF for every position, so keep the OTF
-    // across calls and rebuild it only when the PSF's content hash (or a shape) changes.
     unsigned long long* dhash = reinterpret_cast<unsigned long long*>(psum) + 1;
     unsigned long long hv[3] = {0, 0, 0};
-    const int64_t dims[6] = {pz, py, px, Z, Y, X};
-    // which spectrum layout the plan's kernels keep (an OTF only fits its own) and whether the real form is wanted too
-    const int tag = fftconv_plan_tag(*pl) + (getenv("BH_RL_COMPLEX_OTF") ? 0 : 2);
-    bool same_key = ctx->otf_valid && ctx->otf_tag == tag;
-    for (int i = 0; i < 6; ++i) same_key = same_key && ctx->otf_dims[i] == dims[i];
-    const size_t psf_bytes = (size_t)(pz * py * px) * sizeof(float);
-    uint32_t* kept = nullptr;  // device copy of the PSF the cached OTF was built from
-    BH_TRY(get_scratch(ctx, "rl_psf_kept", psf_bytes, (void**)&kept));
-    // one small kernel + one 16-byte read-back decide the hit: the hash is only a log key, equality of the bytes decides.
-    // (A pointer match would not do instead of the read-back: the adapters upload the PSF anew for every call, and a buffer
-    // that kept its address may have changed its contents.)
-    hipLaunchKernelGGL(content_hash_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(psf),
-                       pz * py * px, same_key ? kept : nullptr, dhash);
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(content_hash_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(psf), K[0] * K[1] * K[2],
+                       kept, dhash);
     BH_CHECK_HIP(hipMemcpyAsync(hv, dhash, sizeof(hv), hipMemcpyDeviceToHost, s));
     BH_CHECK_HIP(hipStreamSynchronize(s));
-    const bool hit = same_key && hv[1] == 1ull;
-    // A PSF with odd extents that equals its point mirror bit for bit (every theoretical PSF; the bench's Gaussian) sits
-    // symmetric about the origin after staging, so its transfer function is REAL: the imaginary parts the transforms leave
-    // are round-off.  The Z passes then read one float per bin instead of two (17.4 -> 8.7 GB per iteration at config 2) and
-    // convolution and correlation are the same pass.  BH_RL_COMPLEX_OTF=1 keeps the general path (A/B switch).
-    const bool real_otf = (pz & 1) && (py & 1) && (px & 1) && hv[2] == 1ull && getenv("BH_RL_COMPLEX_OTF") == nullptr;
-    float* otf_real = nullptr;
-    if (real_otf) BH_TRY(get_scratch(ctx, "fc_otf_real", NS * sizeof(float), (void**)&otf_real));
-    if (!hit) {
-        ctx->otf_valid = false;
-        // the padded PSF is staged in the spectrum buffer's own memory? no: it must survive the forward X pass that
-        // writes the OTF, so it gets a real-volume scratch that is only ever needed on a cache miss
-        BH_TRY(get_scratch(ctx, "fft_real", V * sizeof(float), (void**)&real));
-        BH_TRY(stage_rl_psf(ctx, psf, pz, py, px, Z, Y, X, real, psum));
-        BH_TRY(fftconv_make_otf(ctx, *pl, real, otf));
-        if (real_otf) {
-            hipLaunchKernelGGL(real_part_kernel, grid_for(ctx, (int64_t)NS), dim3(256), 0, s, otf, otf_real, (int64_t)NS);
-            BH_CHECK_HIP(hipGetLastError());
-        }
-        BH_CHECK_HIP(hipMemcpyAsync(kept, psf, psf_bytes, hipMemcpyDeviceToDevice, s));
-        ctx->otf_hash = hv[0];
-        ctx->otf_tag = tag;
-        for (int i = 0; i < 6; ++i) ctx->otf_dims[i] = dims[i];
-        ctx->otf_valid = true;
-    }
-    return rl_engine_run(ctx, pl, d, real_otf ? (const void*)otf_real : (const void*)otf, real_otf, -1, iterations, eps, out);
+    *same = kept != nullptr && hv[1] == 1ull;
+    *real_form = (K[0] & 1) && (K[1] & 1) && (K[2] & 1) && hv[2] == 1ull && getenv("BH_RL_COMPLEX_OTF") == nullptr;
+    return BH_OK;
 }
 
 static bool is_smooth(int64_t n) {  // only the radices hipFFT has native kernels for
@@ -696,12 +636,7 @@ static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
         hipLaunchKernelGGL(remap_kernel<false>, grid2(pad_d.D), dim3(256), 0, s, d, dp, pad_d);
         hipLaunchKernelGGL(remap_kernel<true>, grid2(pad.D), dim3(256), 0, s, d, a, pad);  // e0 = max(d, 0), wrap-extended
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->timing) {
-        BH_CHECK_HIP(hipEventCreate(&e0));
-        BH_CHECK_HIP(hipEventCreate(&e1));
-        BH_CHECK_HIP(hipEventRecord(e0, s));
-    }
+    ScopedIterTimer iter_timer(ctx, T_RL_ITER, iterations);
     float *cur = a, *nxt = b;
     if (wrap) {  // the last pass stores the result cropped: no crop kernel
         BH_TRY(fftconv_richardson_lucy_wrap(ctx, *pl, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, spec_b, a, b, N, K,
@@ -715,43 +650,7 @@ static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
         hipLaunchKernelGGL(remap_kernel<false>, grid2(crop.D), dim3(256), 0, s, (const float*)cur, out, crop);
     }
     BH_CHECK_HIP(hipGetLastError());
-    if (e0) {
-        BH_CHECK_HIP(hipEventRecord(e1, s));
-        BH_CHECK_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        BH_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ctx->ms_override[T_RL_ITER] = ms / iterations;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
     return BH_OK;
-}
-
-static int richardson_lucy_engine_padded(bh_ctx* ctx, const float* d, const float* psf, int64_t pz, int64_t py, int64_t px,
-                                         int64_t Z, int64_t Y, int64_t X, const int64_t P[3], int iterations, float eps,
-                                         float* out) {
-    const int64_t N[3] = {Z, Y, X}, K[3] = {pz, py, px};
-    const int64_t V = Z * Y * X, VP = P[0] * P[1] * P[2];
-    hipStream_t s = ctx->stream;
-    if (iterations == 0) {
-        hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, s, d, out, V);
-        BH_CHECK_HIP(hipGetLastError());
-        return BH_OK;
-    }
-    ConvPlan* pl;
-    BH_TRY(fftconv_plan(ctx, P[0], P[1], P[2], &pl));
-    const size_t NS = fftconv_spectrum_elems(*pl);
-    float* a;
-    cf* otf;
-    double* psum;
-    BH_TRY(get_scratch(ctx, "fft_real", VP * sizeof(float), (void**)&a));
-    BH_TRY(get_scratch(ctx, "fc_otf", NS * sizeof(cf), (void**)&otf));
-    BH_TRY(get_scratch(ctx, "rl_psum", 64, (void**)&psum));
-    ctx->otf_valid = false;  // fc_otf is overwritten: the cache of richardson_lucy_fused no longer holds
-    ScopedTimer timer(ctx, T_RL_TOTAL);
-    BH_TRY(stage_rl_psf(ctx, psf, pz, py, px, P[0], P[1], P[2], a, psum));
-    BH_TRY(fftconv_make_otf(ctx, *pl, a, otf));
-    return rl_padded_run(ctx, pl, d, otf, false, -1, N, K, P, iterations, eps, out);
 }
 
 // Which transform box and back-end Richardson-Lucy uses for a shape (host logic only; bh_richardson_lucy_plan exports it).
@@ -779,6 +678,11 @@ static int rl_plan(int64_t pz, int64_t py, int64_t px, int64_t Z, int64_t Y, int
     }
     for (int a = 0; a < 3; ++a) box[a] = P[a];
     return BH_RL_LIBRARY;
+}
+
+void rl_oneshot_drop(bh_ctx* ctx) {
+    (void)bh_richardson_lucy_destroy(ctx->rl_oneshot);  // owns nothing: its transfer function is scratch
+    ctx->rl_oneshot = nullptr;
 }
 
 }  // namespace bh
@@ -1026,14 +930,15 @@ int bh_tikhonov(bh_ctx* ctx, const float* in, const float* tf_full, int64_t Z, i
 }
 
 
-// Richardson-Lucy for a volume with an awkward axis (a large prime factor makes hipFFT fall back to Bluestein: the
+// The library (hipFFT) loop, and Richardson-Lucy for a volume with an awkward axis (a large prime factor makes hipFFT fall back to Bluestein: the
 // deskewed (342, 1024, 1517) runs 10x slower per voxel than a power of two).  Awkward axes are zero-padded to the next
 // 7-smooth P >= N + K - 1 and the wrapped-around part of the linear convolution is folded back, which is exactly the
 // circular convolution at size N the definition asks for; smooth axes keep P = N and wrap by themselves.
-static int richardson_lucy_padfold(bh_ctx* ctx, const float* d, const float* psf, int64_t pz, int64_t py, int64_t px,
-                                   int64_t Z, int64_t Y, int64_t X, const int64_t P[3], int iterations, float eps,
-                                   float* out) {
-    const int64_t N[3] = {Z, Y, X}, K[3] = {pz, py, px};
+// With box == volume (every axis smooth) nothing is padded: the estimate is transformed where it lies and the plain ratio and
+// update kernels run instead of the pad / fold ones, which would cost two more passes per iteration.
+static int rl_library_run(bh_ctx* ctx, const float* d, const float* psf, const int64_t K[3], const int64_t N[3], const int64_t P[3],
+                          int iterations, float eps, float* out) {
+    const bool fold = P[0] != N[0] || P[1] != N[1] || P[2] != N[2];
     FoldDims conv, corr;
     for (int a = 0; a < 3; ++a) {
         conv.N[a] = corr.N[a] = N[a];
@@ -1044,56 +949,43 @@ static int richardson_lucy_padfold(bh_ctx* ctx, const float* d, const float* psf
         corr.elo[a] = conv.ehi[a];                               // the correlation kernel is the mirror image
         corr.ehi[a] = conv.elo[a];
     }
-    const int64_t V = Z * Y * X, VP = P[0] * P[1] * P[2], NS = P[0] * P[1] * (P[2] / 2 + 1);
+    const int64_t V = N[0] * N[1] * N[2], VP = P[0] * P[1] * P[2], NS = P[0] * P[1] * (P[2] / 2 + 1);
     FftPlans* pl;
     BH_TRY(get_plans(ctx, P[0], P[1], P[2], &pl));
-    float *ra, *rb;
+    float *ra, *rb = nullptr;
     cf *spec, *otf;
     double* psum;
     BH_TRY(get_scratch(ctx, "fft_real", VP * sizeof(float), (void**)&ra));
-    BH_TRY(get_scratch(ctx, "rl_real2", VP * sizeof(float), (void**)&rb));
+    if (fold) BH_TRY(get_scratch(ctx, "rl_real2", VP * sizeof(float), (void**)&rb));
     BH_TRY(get_scratch(ctx, "fft_spec", NS * sizeof(cf), (void**)&spec));
     BH_TRY(get_scratch(ctx, "rl_otf", NS * sizeof(cf), (void**)&otf));
     BH_TRY(get_scratch(ctx, "rl_psum", 64, (void**)&psum));
     hipStream_t s = ctx->stream;
-    ScopedTimer timer(ctx, T_RL_TOTAL);
-    BH_CHECK_HIP(hipMemsetAsync(ra, 0, VP * sizeof(float), s));
-    hipLaunchKernelGGL(psf_sum_kernel, dim3(1), dim3(256), 0, s, psf, pz * py * px, psum);
-    hipLaunchKernelGGL(place_psf_kernel, grid_for(ctx, pz * py * px), dim3(256), 0, s, psf, ra, (int)pz, (int)py, (int)px,
-                       P[0], P[1], P[2], 0, 0, 0, (int)(pz / 2), (int)(py / 2), (int)(px / 2), (const double*)psum);
+    // OTF = rfftn(roll(pad(psf / sum), -centre)) / VP   (the 1/VP makes every C2R normalised)
+    BH_TRY(stage_rl_psf(ctx, psf, K[0], K[1], K[2], P[0], P[1], P[2], ra, psum));
     BH_TRY(fft_forward(pl, ra, otf));
     hipLaunchKernelGGL(scale_spectrum_kernel, grid_for(ctx, NS), dim3(256), 0, s, otf, NS, (float)(1.0 / (double)VP));
-    hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, s, d, out, V);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->timing && iterations > 0) {
-        BH_CHECK_HIP(hipEventCreate(&e0));
-        BH_CHECK_HIP(hipEventCreate(&e1));
-        BH_CHECK_HIP(hipEventRecord(e0, s));
-    }
+    hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, s, d, out, V);  // e0 = max(d, 0)
+    ScopedIterTimer iter_timer(ctx, T_RL_ITER, iterations);
     const int64_t n2 = NS / 2;
+    auto product = [&](auto conj) {  // spec *= otf, or its conjugate
+        hipLaunchKernelGGL(cmul_kernel<decltype(conj)::value>, grid_for(ctx, n2), dim3(256), 0, s, spec, otf, n2);
+        if (NS & 1) hipLaunchKernelGGL(cmul_tail_kernel<decltype(conj)::value>, dim3(1), dim3(1), 0, s, spec, otf, NS - 1);
+    };
     for (int it = 0; it < iterations; ++it) {
-        hipLaunchKernelGGL(pad_volume_kernel, grid_for(ctx, VP), dim3(256), 0, s, (const float*)out, ra, conv);
-        BH_TRY(fft_forward(pl, ra, spec));
-        hipLaunchKernelGGL(cmul_kernel<false>, grid_for(ctx, n2), dim3(256), 0, s, spec, otf, n2);
-        if (NS & 1) hipLaunchKernelGGL(cmul_tail_kernel<false>, dim3(1), dim3(1), 0, s, spec, otf, NS - 1);
+        if (fold) hipLaunchKernelGGL(pad_volume_kernel, grid_for(ctx, VP), dim3(256), 0, s, (const float*)out, ra, conv);
+        BH_TRY(fft_forward(pl, fold ? ra : out, spec));
+        product(std::false_type{});
         BH_TRY(fft_inverse(pl, spec, ra));
-        hipLaunchKernelGGL(fold_ratio_kernel, grid_for(ctx, VP), dim3(256), 0, s, (const float*)ra, d, rb, conv, eps);
-        BH_TRY(fft_forward(pl, rb, spec));
-        hipLaunchKernelGGL(cmul_kernel<true>, grid_for(ctx, n2), dim3(256), 0, s, spec, otf, n2);
-        if (NS & 1) hipLaunchKernelGGL(cmul_tail_kernel<true>, dim3(1), dim3(1), 0, s, spec, otf, NS - 1);
+        if (fold) hipLaunchKernelGGL(fold_ratio_kernel, grid_for(ctx, VP), dim3(256), 0, s, (const float*)ra, d, rb, conv, eps);
+        else hipLaunchKernelGGL(ratio_kernel, grid_for(ctx, V / 4 + 1), dim3(256), 0, s, ra, d, V, eps);
+        BH_TRY(fft_forward(pl, fold ? rb : ra, spec));
+        product(std::true_type{});
         BH_TRY(fft_inverse(pl, spec, ra));
-        hipLaunchKernelGGL(fold_update_kernel, grid_for(ctx, V), dim3(256), 0, s, (const float*)ra, out, corr);
+        if (fold) hipLaunchKernelGGL(fold_update_kernel, grid_for(ctx, V), dim3(256), 0, s, (const float*)ra, out, corr);
+        else hipLaunchKernelGGL(update_kernel, grid_for(ctx, V / 4 + 1), dim3(256), 0, s, out, (const float*)ra, V);
     }
     BH_CHECK_HIP(hipGetLastError());
-    if (e0) {
-        BH_CHECK_HIP(hipEventRecord(e1, s));
-        BH_CHECK_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        BH_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ctx->ms_override[T_RL_ITER] = ms / iterations;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
     return BH_OK;
 }
 
@@ -1116,68 +1008,71 @@ struct bh_rl {
     int backend = 0;
     int64_t K[3] = {0, 0, 0}, N[3] = {0, 0, 0}, box[3] = {0, 0, 0};
     bh::ConvPlan* plan = nullptr;
-    void* otf = nullptr;       // engine back-ends: NS complex, or NS floats when otf_real (owned, pooled on destroy)
+    bool owned = true;         // false: `otf` is the context's scratch and `psf` the caller's (the one-shot entry's handle)
+    void* otf = nullptr;       // engine back-ends: NS complex, or NS floats when otf_real (pooled on destroy)
     size_t otf_bytes = 0;
     bool otf_real = false;
     int zr = -1;               // >= 0: `otf` holds the compact z taps of this radius (fftconv_make_ztaps), the Z passes convolve directly
-    float* psf = nullptr;      // library back-end: the PSF itself (the one-shot path rebuilds its library transfer function)
+    float* psf = nullptr;      // library back-end: the PSF itself (rl_library_run builds its transfer function per call)
 };
 
-int bh_richardson_lucy_create(bh_ctx* ctx, const float* psf, int64_t pz, int64_t py, int64_t px, int64_t Z, int64_t Y,
-                              int64_t X, bh_rl** out) {
-    BH_REQUIRE(ctx && psf && out, "NULL argument");
-    BH_REQUIRE(pz > 0 && py > 0 && px > 0 && pz <= Z && py <= Y && px <= X, "PSF must fit inside the volume");
-    BH_CHECK_HIP(hipSetDevice(ctx->device));
+// What distinguishes the callers of rl_create_impl.
+struct RlCreateOpts {
+    bool use_scratch;  // the transfer function lives in the context's scratch ("fc_otf", "fc_otf_real") and the handle owns nothing;
+                       // else in a block of the filter pool, the set-up's transients in scratch going back to the driver
+    bool ztaps;        // fftconv_ztaps_radius may choose the direct Z pass (not with use_scratch: the taps have no scratch of their own)
+    bool real_otf;     // keep the real form: the caller's rl_probe_psf said the PSF has one, and the entry takes it
+};
+
+// The set-up of every Richardson-Lucy entry at the box and back-end rl_plan picked: normalise, pad, centre and transform the
+// PSF, keep the result in the form `opts` asks for.
+static int rl_create_impl(bh_ctx* ctx, const float* psf, const int64_t K[3], const int64_t N[3], const int64_t box[3], int backend,
+                          const RlCreateOpts& opts, bh_rl** out) {
     *out = nullptr;
     bh_rl* h = new bh_rl();
     h->device = ctx->device;
-    h->K[0] = pz, h->K[1] = py, h->K[2] = px;
-    h->N[0] = Z, h->N[1] = Y, h->N[2] = X;
-    h->backend = rl_plan(pz, py, px, Z, Y, X, h->box);
+    h->backend = backend;
+    h->owned = !opts.use_scratch;
+    for (int a = 0; a < 3; ++a) h->K[a] = K[a], h->N[a] = N[a], h->box[a] = box[a];
     hipStream_t s = ctx->stream;
     auto fail = [&](int rc) {
         (void)bh_richardson_lucy_destroy(h);
         return rc;
     };
-    const size_t psf_bytes = (size_t)(pz * py * px) * sizeof(float);
-    if (h->backend == BH_RL_LIBRARY) {
-        if (hipMalloc((void**)&h->psf, psf_bytes) != hipSuccess) return (set_error("out of device memory (PSF copy)"), fail(BH_ERR_HIP));
-        if (hipMemcpyAsync(h->psf, psf, psf_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return (set_error("PSF copy failed"), fail(BH_ERR_HIP));
+    if (backend == BH_RL_LIBRARY) {
+        const size_t psf_bytes = (size_t)(K[0] * K[1] * K[2]) * sizeof(float);
+        if (!h->owned) h->psf = const_cast<float*>(psf);
+        else if (hipMalloc((void**)&h->psf, psf_bytes) != hipSuccess) return (set_error("out of device memory (PSF copy)"), fail(BH_ERR_HIP));
+        else if (hipMemcpyAsync(h->psf, psf, psf_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) return (set_error("PSF copy failed"), fail(BH_ERR_HIP));
         *out = h;
         return BH_OK;
     }
-    int rc = fftconv_plan(ctx, h->box[0], h->box[1], h->box[2], &h->plan);
+    int rc = fftconv_plan(ctx, box[0], box[1], box[2], &h->plan);
     if (rc != BH_OK) return fail(rc);
     const size_t NS = fftconv_spectrum_elems(*h->plan);
-    const int64_t VP = h->box[0] * h->box[1] * h->box[2];
-    // real transfer function?  (a PSF with odd extents that equals its point mirror bit for bit: richardson_lucy_fused)
-    double* psum;
-    if ((rc = get_scratch(ctx, "rl_psum", 64, (void**)&psum)) != BH_OK) return fail(rc);
-    unsigned long long* dhash = reinterpret_cast<unsigned long long*>(psum) + 1;
-    unsigned long long hv[3] = {0, 0, 0};
-    hipLaunchKernelGGL(content_hash_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(psf), pz * py * px,
-                       (const uint32_t*)nullptr, dhash);
-    if (hipMemcpyAsync(hv, dhash, sizeof(hv), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        return (set_error("PSF symmetry check failed"), fail(BH_ERR_HIP));
-    h->otf_real = (pz & 1) && (py & 1) && (px & 1) && hv[2] == 1ull && getenv("BH_RL_COMPLEX_OTF") == nullptr;
+    const int64_t VP = box[0] * box[1] * box[2];
+    h->otf_real = opts.real_otf;
     // the PSF's z-extent fits the compiled taps: R + 1 (real) or 2R + 1 planes of taps instead of the Z planes of the transfer function
-    h->zr = fftconv_ztaps_radius(*h->plan, pz);
+    h->zr = opts.ztaps ? fftconv_ztaps_radius(*h->plan, K[0]) : -1;
     h->otf_bytes = h->zr >= 0 ? fftconv_ztaps_elems(*h->plan, h->zr, h->otf_real) * sizeof(cf) : NS * (h->otf_real ? sizeof(float) : sizeof(cf));
-    if ((h->otf = filter_pool_take(ctx->device, h->otf_bytes)) == nullptr &&
-        dev_alloc(ctx->device, h->otf_bytes, &h->otf) != hipSuccess) {
+    // the complex transfer function is what is kept, or (only its real part or the z taps are) a transient in scratch "fc_otf"
+    const bool transient = h->otf_real || h->zr >= 0;
+    if (opts.use_scratch || transient) rl_oneshot_drop(ctx);  // "fc_otf" is overwritten below: a kept one-shot handle no longer holds
+    if (opts.use_scratch) {
+        if ((rc = get_scratch(ctx, h->otf_real ? "fc_otf_real" : "fc_otf", h->otf_bytes, &h->otf)) != BH_OK) return fail(rc);
+    } else if ((h->otf = filter_pool_take(ctx->device, h->otf_bytes)) == nullptr &&
+               dev_alloc(ctx->device, h->otf_bytes, &h->otf) != hipSuccess) {
         h->otf = nullptr;
         (void)hipGetLastError();
         return (set_error("out of device memory (%zu bytes for the transfer function)", h->otf_bytes), fail(BH_ERR_HIP));
     }
-    // the padded PSF and (for the real form) the complex transfer function are transients in the context's scratch
-    float* real;
+    float* real;  // the padded PSF
+    double* psum;
     cf* otf_c = reinterpret_cast<cf*>(h->otf);
     if ((rc = get_scratch(ctx, "fft_real", VP * sizeof(float), (void**)&real)) != BH_OK) return fail(rc);
-    if (h->otf_real || h->zr >= 0) {
-        if ((rc = get_scratch(ctx, "fc_otf", NS * sizeof(cf), (void**)&otf_c)) != BH_OK) return fail(rc);
-        ctx->otf_valid = false;  // fc_otf is overwritten: the one-shot path's cache no longer holds
-    }
-    if ((rc = stage_rl_psf(ctx, psf, pz, py, px, h->box[0], h->box[1], h->box[2], real, psum)) != BH_OK) return fail(rc);
+    if (transient && (rc = get_scratch(ctx, "fc_otf", NS * sizeof(cf), (void**)&otf_c)) != BH_OK) return fail(rc);
+    if ((rc = get_scratch(ctx, "rl_psum", 64, (void**)&psum)) != BH_OK) return fail(rc);
+    if ((rc = stage_rl_psf(ctx, psf, K[0], K[1], K[2], box[0], box[1], box[2], real, psum)) != BH_OK) return fail(rc);
     if (h->zr >= 0) {
         if ((rc = fftconv_make_ztaps(ctx, *h->plan, real, h->otf_real, h->zr, otf_c, reinterpret_cast<cf*>(h->otf))) != BH_OK) return fail(rc);
     } else if ((rc = fftconv_make_otf(ctx, *h->plan, real, otf_c)) != BH_OK) {
@@ -1187,12 +1082,60 @@ int bh_richardson_lucy_create(bh_ctx* ctx, const float* psf, int64_t pz, int64_t
                            (int64_t)NS);
         if (hipGetLastError() != hipSuccess) return (set_error("real_part_kernel launch failed"), fail(BH_ERR_HIP));
     }
-    // the transients of the set-up go back to the driver: the complex transfer function when only its real part is kept (and
-    // with it the one-shot path's cache), the padded PSF when the apply path has no use for a real-volume scratch of its own
-    if ((h->otf_real || h->zr >= 0) && (rc = free_scratch(ctx, "fc_otf")) != BH_OK) return fail(rc);
-    if (h->backend == BH_RL_ENGINE && (rc = free_scratch(ctx, "fft_real")) != BH_OK) return fail(rc);
+    // an owning handle gives the transients of the set-up back to the driver: the complex transfer function when only its real
+    // part or taps are kept, the padded PSF when the apply path has no use for a real-volume scratch of its own
+    if (h->owned && transient && (rc = free_scratch(ctx, "fc_otf")) != BH_OK) return fail(rc);
+    if (h->owned && backend == BH_RL_ENGINE && (rc = free_scratch(ctx, "fft_real")) != BH_OK) return fail(rc);
     *out = h;
     return BH_OK;
+}
+
+// The iterations of any handle.  The caller holds the T_RL_TOTAL timer and has kept the data term apart from `out`.
+static int rl_apply_impl(bh_ctx* ctx, const bh_rl* h, const float* d, int iterations, float eps, float* out, double* row_sums,
+                         int* produced) {
+    if (h->backend == BH_RL_LIBRARY) return rl_library_run(ctx, d, h->psf, h->K, h->N, h->box, iterations, eps, out);
+    if (h->backend == BH_RL_ENGINE) {
+        // the last update pass can leave the row sums of its result behind (what a deskew with a mean fill wants of this volume)
+        if (row_sums) fftconv_arm_rowsums(*h->plan, row_sums);
+        const int st = rl_engine_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, iterations, eps, out);
+        if (row_sums) *produced = fftconv_rowsums_taken(*h->plan) && st == BH_OK ? 1 : 0;
+        return st;
+    }
+    return rl_padded_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, h->N, h->K, h->box, iterations, eps, out);
+}
+
+// What both public entries do before anything else: keep the data term aside when the estimate overwrites it (in == out), and
+// with nothing to iterate on an engine back-end store e0 = max(d, 0) and be `done` (the fused passes write `out` only from
+// iteration 1 on; the library loop clips by itself).
+static int rl_begin(bh_ctx* ctx, const float* in, int64_t V, int backend, int iterations, float* out, const float** d, bool* done) {
+    *d = in;
+    if (in == out) {
+        float* dcopy;
+        BH_TRY(get_scratch(ctx, "rl_data", V * sizeof(float), (void**)&dcopy));
+        BH_CHECK_HIP(hipMemcpyAsync(dcopy, in, V * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+        *d = dcopy;
+    }
+    *done = iterations == 0 && backend != BH_RL_LIBRARY;
+    if (*done) {
+        hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, ctx->stream, *d, out, V);
+        BH_CHECK_HIP(hipGetLastError());
+    }
+    return BH_OK;
+}
+
+int bh_richardson_lucy_create(bh_ctx* ctx, const float* psf, int64_t pz, int64_t py, int64_t px, int64_t Z, int64_t Y,
+                              int64_t X, bh_rl** out) {
+    BH_REQUIRE(ctx && psf && out, "NULL argument");
+    BH_REQUIRE(pz > 0 && py > 0 && px > 0 && pz <= Z && py <= Y && px <= X, "PSF must fit inside the volume");
+    BH_CHECK_HIP(hipSetDevice(ctx->device));
+    *out = nullptr;
+    const int64_t K[3] = {pz, py, px}, N[3] = {Z, Y, X};
+    int64_t box[3];
+    const int backend = rl_plan(pz, py, px, Z, Y, X, box);
+    RlCreateOpts opts = {false, true, false};
+    bool same;
+    if (backend != BH_RL_LIBRARY) BH_TRY(rl_probe_psf(ctx, psf, K, nullptr, &same, &opts.real_otf));
+    return rl_create_impl(ctx, psf, K, N, box, backend, opts, out);
 }
 
 int bh_richardson_lucy_apply(bh_ctx* ctx, const bh_rl* h, const float* in, int iterations, float eps, float* out) {
@@ -1207,37 +1150,18 @@ int bh_richardson_lucy_apply_rows(bh_ctx* ctx, const bh_rl* h, const float* in, 
     BH_REQUIRE(iterations >= 0, "iterations must be >= 0");
     BH_REQUIRE(ctx->device == h->device, "the handle belongs to device %d, the context to device %d", h->device, ctx->device);
     BH_CHECK_HIP(hipSetDevice(ctx->device));
-    const int64_t Z = h->N[0], Y = h->N[1], X = h->N[2], V = Z * Y * X;
-    hipStream_t s = ctx->stream;
-    const float* d = in;
-    if (in == out) {  // the estimate overwrites `out`; keep the data term
-        float* dcopy;
-        BH_TRY(get_scratch(ctx, "rl_data", V * sizeof(float), (void**)&dcopy));
-        BH_CHECK_HIP(hipMemcpyAsync(dcopy, in, V * sizeof(float), hipMemcpyDeviceToDevice, s));
-        d = dcopy;
-    }
-    if (h->backend == BH_RL_LIBRARY)
-        return bh_richardson_lucy(ctx, d, h->psf, h->K[0], h->K[1], h->K[2], Z, Y, X, iterations, eps, out);
-    if (iterations == 0) {
-        hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, s, d, out, V);
-        BH_CHECK_HIP(hipGetLastError());
-        return BH_OK;
-    }
+    const float* d;
+    bool done;
+    BH_TRY(rl_begin(ctx, in, h->N[0] * h->N[1] * h->N[2], h->backend, iterations, out, &d, &done));
+    if (done) return BH_OK;
     ScopedTimer timer(ctx, T_RL_TOTAL);
-    if (h->backend == BH_RL_ENGINE) {
-        // the last update pass can leave the row sums of its result behind (what a deskew with a mean fill wants of this volume)
-        if (row_sums) fftconv_arm_rowsums(*h->plan, row_sums);
-        const int st = rl_engine_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, iterations, eps, out);
-        if (row_sums) *produced = fftconv_rowsums_taken(*h->plan) && st == BH_OK ? 1 : 0;
-        return st;
-    }
-    return rl_padded_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, h->N, h->K, h->box, iterations, eps, out);
+    return rl_apply_impl(ctx, h, d, iterations, eps, out, row_sums, produced);
 }
 
 int bh_richardson_lucy_destroy(bh_rl* h) {
     if (!h) return BH_OK;
-    if (h->otf) filter_pool_give(h->device, h->otf_bytes, h->otf);
-    if (h->psf) (void)hipFree(h->psf);
+    if (h->owned && h->otf) filter_pool_give(h->device, h->otf_bytes, h->otf);
+    if (h->owned && h->psf) (void)hipFree(h->psf);
     delete h;
     return BH_OK;
 }
@@ -1259,81 +1183,53 @@ int bh_richardson_lucy_zpass(const bh_rl* h, int* direct, int* taps) {
     return BH_OK;
 }
 
+// One-shot form: a handle whose transfer function lives in the context's scratch, then the iterations every handle runs.  On
+// the engine box the handle is kept for the next call and validated against the PSF's bytes on every call (rl_probe_psf: the
+// stall bh_richardson_lucy_create / _apply does without); a plate reuses one PSF for every position.  The wrap-padded and
+// library boxes set up anew on every call, and the wrap-padded one always keeps the complex form, point-symmetric PSF or not:
+// no entry computes anything but what it always did.
 int bh_richardson_lucy(bh_ctx* ctx, const float* in, const float* psf, int64_t pz, int64_t py, int64_t px, int64_t Z,
                        int64_t Y, int64_t X, int iterations, float eps, float* out) {
     BH_REQUIRE(ctx && in && psf && out, "NULL argument");
     BH_REQUIRE(iterations >= 0, "iterations must be >= 0");
     BH_REQUIRE(pz > 0 && py > 0 && px > 0 && pz <= Z && py <= Y && px <= X, "PSF must fit inside the volume");
     BH_CHECK_HIP(hipSetDevice(ctx->device));
-    const int64_t V = Z * Y * X, Xh = X / 2 + 1, NS = Z * Y * Xh;
-    float *real, *dcopy = nullptr;
-    hipStream_t s = ctx->stream;
-    const float* d = in;
-    if (in == out) {  // the estimate overwrites `out`; keep the data term
-        BH_TRY(get_scratch(ctx, "rl_data", V * sizeof(float), (void**)&dcopy));
-        BH_CHECK_HIP(hipMemcpyAsync(dcopy, in, V * sizeof(float), hipMemcpyDeviceToDevice, s));
-        d = dcopy;
-    }
+    const int64_t K[3] = {pz, py, px}, N[3] = {Z, Y, X};
     int64_t box[3];
     const int backend = rl_plan(pz, py, px, Z, Y, X, box);
-    if (backend == BH_RL_ENGINE) return richardson_lucy_fused(ctx, d, psf, pz, py, px, Z, Y, X, iterations, eps, out);
-    if (backend == BH_RL_ENGINE_PADDED)
-        return richardson_lucy_engine_padded(ctx, d, psf, pz, py, px, Z, Y, X, box, iterations, eps, out);
-    if (box[0] != Z || box[1] != Y || box[2] != X)
-        return richardson_lucy_padfold(ctx, d, psf, pz, py, px, Z, Y, X, box, iterations, eps, out);
-    FftPlans* pl;
-    BH_TRY(get_plans(ctx, Z, Y, X, &pl));
-    cf *spec, *otf;
-    double* psum;
-    BH_TRY(get_scratch(ctx, "fft_real", V * sizeof(float), (void**)&real));
-    BH_TRY(get_scratch(ctx, "fft_spec", NS * sizeof(cf), (void**)&spec));
-    BH_TRY(get_scratch(ctx, "rl_otf", NS * sizeof(cf), (void**)&otf));
-    BH_TRY(get_scratch(ctx, "rl_psum", 64, (void**)&psum));
+    const float* d;
+    bool done;
+    BH_TRY(rl_begin(ctx, in, Z * Y * X, backend, iterations, out, &d, &done));
+    if (done) return BH_OK;
     ScopedTimer timer(ctx, T_RL_TOTAL);
-    // OTF = rfftn(roll(pad(psf / sum), -centre)) / V   (the 1/V makes every C2R normalised)
-    BH_CHECK_HIP(hipMemsetAsync(real, 0, V * sizeof(float), s));
-    hipLaunchKernelGGL(psf_sum_kernel, dim3(1), dim3(256), 0, s, psf, pz * py * px, psum);
-    int bz, by, bx;
-    pad_before(pz, Z, &bz);
-    pad_before(py, Y, &by);
-    pad_before(px, X, &bx);
-    hipLaunchKernelGGL(place_psf_kernel, grid_for(ctx, pz * py * px), dim3(256), 0, s, psf, real, (int)pz, (int)py,
-                       (int)px, Z, Y, X, bz, by, bx, bz + (int)(pz / 2), by + (int)(py / 2), bx + (int)(px / 2),
-                       (const double*)psum);
-    BH_TRY(fft_forward(pl, real, otf));
-    hipLaunchKernelGGL(scale_spectrum_kernel, grid_for(ctx, NS), dim3(256), 0, s, otf, NS, (float)(1.0 / (double)V));
-    // e0 = max(d, 0)
-    hipLaunchKernelGGL(clip_copy_kernel, grid_for(ctx, V), dim3(256), 0, s, d, out, V);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->timing && iterations > 0) {
-        BH_CHECK_HIP(hipEventCreate(&e0));
-        BH_CHECK_HIP(hipEventCreate(&e1));
-        BH_CHECK_HIP(hipEventRecord(e0, s));
+    bh_rl* h = ctx->rl_oneshot;
+    RlCreateOpts opts = {true, false, false};
+    bool hit = false;
+    const size_t psf_bytes = (size_t)(pz * py * px) * sizeof(float);
+    uint32_t* kept = nullptr;  // device copy of the PSF the kept handle was built from
+    if (backend == BH_RL_ENGINE) {
+        ConvPlan* pl;  // stands for the box and for the spectrum layout its kernels keep (fftconv_plan_tag): an OTF only fits its own
+        BH_TRY(fftconv_plan(ctx, Z, Y, X, &pl));
+        bool same_key = h != nullptr && h->plan == pl;
+        for (int a = 0; a < 3; ++a) same_key = same_key && h->K[a] == K[a] && h->N[a] == N[a];
+        BH_TRY(get_scratch(ctx, "rl_psf_kept", psf_bytes, (void**)&kept));
+        BH_TRY(rl_probe_psf(ctx, psf, K, same_key ? kept : nullptr, &hit, &opts.real_otf));
+        hit = hit && h->otf_real == opts.real_otf;
     }
-    const int64_t n2 = NS / 2;
-    for (int it = 0; it < iterations; ++it) {
-        BH_TRY(fft_forward(pl, out, spec));
-        hipLaunchKernelGGL(cmul_kernel<false>, grid_for(ctx, n2), dim3(256), 0, s, spec, otf, n2);
-        if (NS & 1) hipLaunchKernelGGL(cmul_tail_kernel<false>, dim3(1), dim3(1), 0, s, spec, otf, NS - 1);
-        BH_TRY(fft_inverse(pl, spec, real));
-        hipLaunchKernelGGL(ratio_kernel, grid_for(ctx, V / 4 + 1), dim3(256), 0, s, real, d, V, eps);
-        BH_TRY(fft_forward(pl, real, spec));
-        hipLaunchKernelGGL(cmul_kernel<true>, grid_for(ctx, n2), dim3(256), 0, s, spec, otf, n2);
-        if (NS & 1) hipLaunchKernelGGL(cmul_tail_kernel<true>, dim3(1), dim3(1), 0, s, spec, otf, NS - 1);
-        BH_TRY(fft_inverse(pl, spec, real));
-        hipLaunchKernelGGL(update_kernel, grid_for(ctx, V / 4 + 1), dim3(256), 0, s, out, real, V);
+    if (!hit) {  // (an engine set-up drops the kept handle before it rebuilds in the same scratch; a library one leaves it alone)
+        BH_TRY(rl_create_impl(ctx, psf, K, N, box, backend, opts, &h));
+        if (backend == BH_RL_ENGINE) {
+            ctx->rl_oneshot = h;
+            if (hipMemcpyAsync(kept, psf, psf_bytes, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
+                rl_oneshot_drop(ctx);
+                set_error("PSF copy failed");
+                return BH_ERR_HIP;
+            }
+        }
     }
-    BH_CHECK_HIP(hipGetLastError());
-    if (e0) {
-        BH_CHECK_HIP(hipEventRecord(e1, s));
-        BH_CHECK_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        BH_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ctx->ms_override[T_RL_ITER] = ms / iterations;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    return BH_OK;
+    const int rc = rl_apply_impl(ctx, h, d, iterations, eps, out, nullptr, nullptr);
+    if (h != ctx->rl_oneshot) (void)bh_richardson_lucy_destroy(h);
+    return rc;
 }
 
 }  // extern "C"

@@ -147,8 +147,9 @@ class PreparedRichardsonLucy:
     """Richardson-Lucy with the transfer function of one PSF built once for one volume shape (``bh_richardson_lucy_create``)
     and applied to any number of volumes — the shape of the reference's deconvolve, which computes the transfer function
     once per plate and hands it to every (position, t, c) unit (biahub/deconvolve.py:140-149, 183-191).  A call only
-    enqueues kernels on the current stream: no read-back, no host synchronisation (the one-shot ``richardson_lucy`` validates
-    its cached transfer function against the PSF's bytes on every call), so an upload / compute / download pipeline overlaps.
+    enqueues kernels on the current stream: no read-back, no host synchronisation (the one-shot ``richardson_lucy`` is the
+    same handle kept in the context's scratch, set up anew or, on the engine box, validated against the PSF's bytes on every
+    call, which reads back and synchronises), so an upload / compute / download pipeline overlaps.
     """
 
     def __init__(self, psf_zyx, zyx_shape, device="cuda"):

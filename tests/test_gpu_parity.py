@@ -2208,6 +2208,138 @@ def test_prepared_richardson_lucy_handle(gpu, shape, pshape, backend, monkeypatc
     assert rel_err(c[1], O.richardson_lucy_zyx(vols[1], sym, iterations=3, eps=1e-6)) <= FFT_TOL
 
 
+# the routes of the Richardson-Lucy host layer: volume shape, PSF shape, switches that select the route, back-end
+RL_ROUTES = {
+    "engine": ((16, 64, 128), (5, 5, 7), {}, "engine"),
+    "engine-wave-private": ((8, 64, 1024), (3, 3, 9), {}, "engine"),
+    "padded-fold": ((21, 64, 150), (7, 5, 9), {}, "engine-padded"),                 # wrap-padded box, fold pass
+    "padded-wrap": ((12, 32, 500), (5, 3, 7), {}, "engine-padded"),                 # wrap-padded box, no fold pass
+    "library": ((15, 21, 25), (5, 3, 3), {}, "library"),                            # hipFFT at the volume's own box
+    "library-fold": ((19, 40, 134), (5, 3, 11), {"BH_RL_ENGINE_PAD": "0"}, "library"),  # hipFFT, pad and fold
+}
+
+
+def _rl_route(name, symmetric, monkeypatch, seed=31):
+    """(volume, PSF) of a route as numpy arrays, its switches set."""
+    shape, pshape, env, _ = RL_ROUTES[name]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    psf = O.gaussian_psf(pshape, tuple(max(p / 4.0, 0.8) for p in pshape))
+    if not symmetric:
+        psf[0, 0, 0] += 0.02
+    return O.synthetic_volume(shape, seed=seed, n_blobs=8), psf
+
+
+def _rl_handle_result(name, vol, psf, gpu, iterations=3):
+    """What a prepared handle makes of the volume; the handle must be of the route's back-end."""
+    from biahub_amd.deconvolve import PreparedRichardsonLucy
+
+    with PreparedRichardsonLucy(psf, vol.shape, gpu) as h:
+        assert h.backend == RL_ROUTES[name][3], (name, h.backend)
+        if name == "library-fold":
+            assert h.box != tuple(vol.shape)
+        if name == "library":
+            assert h.box == tuple(vol.shape)
+        return h(torch.from_numpy(vol).to(gpu), iterations, 1e-6)
+
+
+@pytest.mark.parametrize("route,symmetric", [
+    ("engine", True), ("engine", False), ("engine-wave-private", True),
+    # (a symmetric PSF at a padded box is not here: the handle keeps the real form there, the one-shot entry the complex one)
+    ("padded-fold", False), ("padded-wrap", False), ("library", False), ("library-fold", False)])
+def test_richardson_lucy_one_shot_equals_handle_bitwise(gpu, route, symmetric, monkeypatch):
+    """The one-shot entry is a handle in scratch plus the apply every handle runs: with the direct Z pass off (the one-shot
+    keeps the full transfer function) both give the same bits on every route."""
+    from biahub_amd.deconvolve import richardson_lucy
+
+    monkeypatch.setenv("BH_RL_ZDIRECT", "0")
+    vol, psf = _rl_route(route, symmetric, monkeypatch)
+    want = _rl_handle_result(route, vol, psf, gpu)
+    got = richardson_lucy(torch.from_numpy(vol).to(gpu), torch.from_numpy(psf).to(gpu), 3, 1e-6)
+    assert torch.equal(got, want), (route, rel_err(got.cpu().numpy(), want.cpu().numpy()))
+
+
+def test_richardson_lucy_one_shot_cache_follows_its_inputs(gpu, monkeypatch):
+    """One context, one-shot calls in a row: the kept transfer function is rebuilt when the PSF's bytes change behind the same
+    address, when another route or a handle's set-up used its scratch, and serves the first PSF again afterwards.  Every
+    result equals, bit for bit, a prepared handle's (references computed before the sequence)."""
+    from biahub_amd.deconvolve import PreparedRichardsonLucy, richardson_lucy
+
+    monkeypatch.setenv("BH_RL_ZDIRECT", "0")
+    vol_e, sym = _rl_route("engine", True, monkeypatch)
+    asym = _rl_route("engine", False, monkeypatch)[1]
+    vol_p, psf_p = _rl_route("padded-fold", False, monkeypatch)
+    vol_l, psf_l = _rl_route("library", False, monkeypatch)
+    want_sym = _rl_handle_result("engine", vol_e, sym, gpu)
+    want_asym = _rl_handle_result("engine", vol_e, asym, gpu)
+    want_p = _rl_handle_result("padded-fold", vol_p, psf_p, gpu)
+    want_l = _rl_handle_result("library", vol_l, psf_l, gpu)
+
+    def one_shot(vol, psf):
+        return richardson_lucy(torch.from_numpy(vol).to(gpu), psf if torch.is_tensor(psf) else torch.from_numpy(psf).to(gpu), 3, 1e-6)
+
+    pt = torch.from_numpy(sym).to(gpu)
+    first = one_shot(vol_e, pt)
+    assert torch.equal(first, want_sym)
+    pt.copy_(torch.from_numpy(asym))                       # same address, new bytes
+    assert torch.equal(one_shot(vol_e, pt), want_asym)
+    assert torch.equal(one_shot(vol_p, psf_p), want_p)
+    assert torch.equal(one_shot(vol_l, psf_l), want_l)
+    PreparedRichardsonLucy(sym, vol_e.shape, gpu).close()  # its set-up uses and frees the scratch of the one-shot's transfer function
+    pt.copy_(torch.from_numpy(sym))
+    last = one_shot(vol_e, pt)
+    assert torch.equal(last, want_sym) and torch.equal(last, first)
+    PreparedRichardsonLucy(sym, vol_e.shape, gpu).close()  # once more, now with a kept transfer function to lose
+    assert torch.equal(one_shot(vol_e, pt), first)
+
+
+def test_richardson_lucy_handle_applies_what_it_created(gpu, monkeypatch):
+    """A handle runs the back-end and box it reports, whatever the switches say by the time it is applied."""
+    from biahub_amd.deconvolve import PreparedRichardsonLucy, richardson_lucy
+
+    vol, psf = _rl_route("engine", False, monkeypatch)
+    v, pt = torch.from_numpy(vol).to(gpu), torch.from_numpy(psf).to(gpu)
+    monkeypatch.setenv("BH_FFT_BACKEND", "hipfft")
+    with PreparedRichardsonLucy(psf, vol.shape, gpu) as h:
+        assert h.backend == "library"
+        want = richardson_lucy(v, pt, 3, 1e-6)
+        monkeypatch.delenv("BH_FFT_BACKEND")
+        assert torch.equal(h(v, 3, 1e-6), want)
+    with PreparedRichardsonLucy(psf, vol.shape, gpu) as h:
+        assert h.backend == "engine"
+        want = h(v, 3, 1e-6)
+        monkeypatch.setenv("BH_FFT_BACKEND", "hipfft")
+        assert torch.equal(h(v, 3, 1e-6), want)
+
+
+@pytest.mark.parametrize("route", ["engine", "padded-fold", "padded-wrap", "library"])
+def test_richardson_lucy_iteration_timer(gpu, route, monkeypatch):
+    """With timing on, every route leaves one iteration's share of the call in T_RL_ITER: finite, positive, and no longer than
+    the whole call (T_RL_TOTAL), of which it is a part.  Nothing to iterate: max(d, 0), and the timer stays out of it."""
+    import math
+
+    from biahub_amd import _lib
+    from biahub_amd.deconvolve import PreparedRichardsonLucy, richardson_lucy
+    from biahub_amd.device import get_context
+
+    vol, psf = _rl_route(route, False, monkeypatch)
+    v, pt = torch.from_numpy(vol).to(gpu), torch.from_numpy(psf).to(gpu)
+    ctx = get_context(gpu)
+    was = ctx.timing
+    try:
+        ctx.set_timing(True)
+        with PreparedRichardsonLucy(psf, vol.shape, gpu) as h:
+            assert h.backend == RL_ROUTES[route][3]
+            for call in (lambda it: richardson_lucy(v, pt, it, 1e-6), lambda it: h(v, it, 1e-6)):
+                call(4)
+                per_iteration, total = ctx.elapsed_ms(_lib.T_RL_ITER), ctx.elapsed_ms(_lib.T_RL_TOTAL)
+                print(f"{route}: {per_iteration:.4f} ms per iteration, {total:.4f} ms in all")
+                assert math.isfinite(per_iteration) and 0 < per_iteration <= total, (route, per_iteration, total)
+                assert np.array_equal(call(0).cpu().numpy(), np.maximum(vol, 0))
+    finally:
+        ctx.set_timing(was)
+
+
 # ----------------------------------------------------------------------------- oracle parity at the bench size
 def test_config2_full_size_oracle_parity(gpu):
     """BASELINE config 2 at its own size against the oracle — the exact kernel instantiations bench.py runs
