@@ -30,7 +30,7 @@ _FC = ("fftconv.hpp", "fftconv_dev.hpp")
 INCLUDES = {"fftconv.hip": _FC, "fftconv_col.hip": _FC, "fftconv_xtile.hip": _FC + ("fftconv_xpass.inc",), "fftconv_xw.hip": _FC + ("fftconv_xw.inc", "fftconv_x3.inc"),
             "fftconv_colreg.hip": _FC + ("fftconv_xw.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"),
             "deconv.hip": ("fftconv.hpp",), "invtf.hip": ("fftconv.hpp",), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
-            "deskew.hip": ("deskew_rows.inc",), "zstd.hip": ("zstd_frame.inc", "zstd_block.inc")}
+            "deskew.hip": ("deskew_geom.hpp", "deskew_rows.inc"), "host_deskew.hip": ("deskew_geom.hpp",), "zstd.hip": ("zstd_frame.inc", "zstd_block.inc")}
 
 
 def needs_build() -> bool:

@@ -1,5 +1,4 @@
-// One-pass overhang fill of the deskew (bh_deskew with a fill, float32 volumes the persistent kernel takes) — included by
-// deskew.hip.  The reference fills in three steps on the finished volume (biahub/deskew.py:339-368): mask = (out == 0), three
+// One-pass overhang fill of the deskew (bh_deskew with a fill, every input type) — included by deskew.hip.  The reference fills in three steps on the finished volume (biahub/deskew.py:339-368): mask = (out == 0), three
 // 3x3x3 dilations, fill = mean(out[~mask]) (or a constant), out[mask] = fill.  Unless the DATA holds exact zeros, all of it
 // follows from the geometry and from sums of the input:
 //   * out[a, y', x'] is an exact zero iff the N taps of (a, x') all fall outside the scanned range — a pattern G[a][x'] that does
@@ -12,14 +11,7 @@
 // The resampling kernel then knows the fill value when it starts and writes whole rows (deskew_pers_kernel<NK, 2>).
 namespace rows {
 
-struct Bits {
-    uint32_t* g;   // [Za][WB] geometric zeros (pad bits past Xp set)
-    uint32_t* dg;  // [Za][WB] dilated by 3 in a and x' (pad bits set)
-    int WB;
-};
-
 // one thread per (a, word)
-template <int DUMMY = 0>
 __global__ void geom_bits_kernel(DeskewGeom g, uint32_t* __restrict__ gb, int WB) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -31,11 +23,9 @@ __global__ void geom_bits_kernel(DeskewGeom g, uint32_t* __restrict__ gb, int WB
         bool zero = true;
         if (xo < g.Xp) {
             for (int k = 0; k < g.N; ++k) {
-                const float ix = deskew_ix(g.px, g.pxct, g.offset, g.zm1, xo, a * g.N + k);
-                const float fl = floorf(ix);
-                const int z0 = (int)fl;
-                const bool lower = z0 >= 0 && z0 < g.Z;                          // weight (fl + 1) - ix > 0 always
-                const bool upper = z0 + 1 >= 0 && z0 + 1 < g.Z && (ix - fl) != 0.0f;
+                const DeskewTaps t = deskew_taps(g, xo, a * g.N + k);
+                const bool lower = t.z0 >= 0 && t.z0 < g.Z;  // its weight w0 > 0 always
+                const bool upper = t.z0 + 1 >= 0 && t.z0 + 1 < g.Z && t.w1 != 0.0f;
                 if (lower || upper) zero = false;
             }
         }
@@ -116,13 +106,11 @@ __global__ __launch_bounds__(256) void mean_partial_kernel(DeskewGeom g, const u
         double t = 0.0;
         for (int k = 0; k < g.N; ++k) {
             const int zo = a * g.N + k;
-            const float ix = deskew_ix(g.px, g.pxct, g.offset, g.zm1, xo, zo);
-            const float fl = floorf(ix);
-            const float w1 = ix - fl, w0 = (fl + 1.0f) - ix;
-            const int z0 = (int)fl;
+            const DeskewTaps tp = deskew_taps(g, xo, zo);
+            const int z0 = tp.z0;
             const int yin = g.Y - 1 - min(zo, g.Y - 1);
-            if (z0 >= 0 && z0 < g.Z) t += (double)w0 * R[(long)z0 * g.Y + yin];
-            if (z0 + 1 >= 0 && z0 + 1 < g.Z) t += (double)w1 * R[(long)(z0 + 1) * g.Y + yin];
+            if (z0 >= 0 && z0 < g.Z) t += (double)tp.w0 * R[(long)z0 * g.Y + yin];
+            if (z0 + 1 >= 0 && z0 + 1 < g.Z) t += (double)tp.w1 * R[(long)(z0 + 1) * g.Y + yin];
         }
         s += t;
     }

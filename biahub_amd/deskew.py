@@ -90,10 +90,10 @@ def fast_deskew_zyx(
     ``raw_data`` is a tensor already on the GPU (float32 like the reference, or
     uint8/uint16/int16 which the kernel widens on load).  Returns a float32 tensor
     ``(ceil(Y/N), X, Xp)`` on the same device.  One kernel replaces the reference's
-    permute/flip copy, edge pad, grid build, ``grid_sample`` and mean.  ``overhang_fill`` other than 0: float32 volumes
-    take the one-pass fill of ``csrc/deskew_rows.inc`` (fill value from row sums of the input, whole rows written once; the
-    bit-mask pipeline of ``csrc/fill.hip`` re-runs the volume only when the data held exact zeros), other inputs the mask
-    pipeline.  ``row_sums`` (float64 ``(Z, Y)`` on the device: sums over x of ``raw_data``) may be handed in by whoever
+    permute/flip copy, edge pad, grid build, ``grid_sample`` and mean.  ``overhang_fill`` other than 0: every input type
+    takes the one-pass fill of ``csrc/deskew_rows.inc`` (fill value from row sums of the input, whole rows written once; the
+    bit-mask pipeline of ``csrc/fill.hip`` re-runs the volume only when the data held exact zeros; ``BH_DESKEW_ONEPASS=0``
+    runs the mask pipeline alone).  ``row_sums`` (float64 ``(Z, Y)`` on the device: sums over x of ``raw_data``) may be handed in by whoever
     produced the volume (``PreparedRichardsonLucy.apply(..., row_sums=...)``); it saves the one read that reduces them.
     """
     if not isinstance(raw_data, torch.Tensor):

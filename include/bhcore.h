@@ -234,7 +234,7 @@ int bh_deskew(bh_ctx* ctx, const void* in, int in_dtype, int64_t Z, int64_t Y, i
               int fill_mode, float fill_value, float* out, float* mean_out);
 
 /* bh_deskew with the row sums of the input handed in: row_sums (device, may be NULL) = float64 [Z * Y], row_sums[z * Y + y] =
- * sum over x of in[z, y, x].  With a "mean" fill of a float32 volume the fill value is derived from them before the resampling
+ * sum over x of in[z, y, x].  With a "mean" fill (any in_dtype) the fill value is derived from them before the resampling
  * kernel starts (which then writes whole rows, fill included, in one pass); an operator that has just produced `in` can
  * reduce them on the way (bh_richardson_lucy_apply_rows), otherwise bh_deskew reduces them itself in one read of `in`. */
 int bh_deskew_rows(bh_ctx* ctx, const void* in, int in_dtype, int64_t Z, int64_t Y, int64_t X,

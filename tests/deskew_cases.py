@@ -272,13 +272,16 @@ def forced_cases():
 # walks ceil(ntiles / CUs) consecutive tiles.  The first geometry has 2 400 tiles, 1 104 of them overhang (runs of them for
 # ``advance`` and ``emit`` to cross).  The two (24, 40x, 128) geometries have 536: three consecutive tiles per workgroup on the 179
 # workgroups that get any, but fewer than 3 x 256 in all, so (24, 576, 128) and (24, 575, 128) — the same geometry, 1 152 tiles —
-# stand beside them for the test's ``ntiles >= 3 x multi_processor_count``.
+# stand beside them for the test's ``ntiles >= 3 x multi_processor_count``.  The last two rows walk the N = 2 and N = 4 kernels (800
+# tiles, 316 of them overhang, two buffers of 68 640 B; 1 200 tiles, 716 overhang, 139 360 B).
 PERSISTENT = [
     ((48, 400, 128), 36.17, 0.25, 1, 2400),
     ((24, 402, 128), 36.17, 0.371, 3, 536),     # Y % N == 0
     ((24, 401, 128), 36.17, 0.371, 3, 536),     # ragged last slab: one replicated row
     ((24, 576, 128), 36.17, 0.371, 3, 1152),
     ((24, 575, 128), 36.17, 0.371, 3, 1152),    # ragged last slab
+    ((16, 400, 128), 36.17, 0.25, 2, 800),      # N = 2 and N = 4: the instantiations the (N, fill mode) launch table could mis-map
+    ((16, 800, 128), 36.17, 0.25, 4, 1200),
 ]
 PERSISTENT_DECLINED = ((240, 8, 64), 36.17, 0.9, 4)      # two buffers of 242 KB
 CUS = 256

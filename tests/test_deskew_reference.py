@@ -127,6 +127,26 @@ def test_oracle_position_under_the_bound(shape, angle, ratio, N, keep, lib_built
         print(f"F64 deskew {shape} N{N} {dtype}: " + " ".join(f"{k} {w:.2f}" for k, w in worst.items()) + f" u M (bound {N + 3})")
 
 
+def test_host_deskew_refuses_an_unknown_dtype_code(lib_built):
+    """A dtype code that is none of the four: ``bh_host_deskew`` returns BH_ERR_INVALID with the message naming the code, at
+    the smallest volume."""
+    import ctypes as C
+
+    from biahub_amd import _lib
+    from biahub_amd.deskew import get_deskewed_data_shape
+
+    shape, angle, ratio = (2, 1, 1), 36.17, 0.371
+    vol = np.ones(shape, np.float32)
+    out = np.zeros(get_deskewed_data_shape(shape, angle, ratio, True)[0], np.float32)
+    for code in (4, -1, 99):
+        assert code not in (_lib.DT_F32, _lib.DT_U16, _lib.DT_U8, _lib.DT_I16)
+        status = _lib.load().bh_host_deskew(vol.ctypes.data_as(C.c_void_p), code, *shape, angle, ratio, 1, 1, _lib.FILL_NONE, 0.0,
+                                            out.ctypes.data_as(C.c_void_p), None, 1)
+        assert status == _lib.BH_ERR_INVALID and _lib.last_error() == f"unsupported input dtype code {code}"
+        with pytest.raises(ValueError, match=f"unsupported input dtype code {code}"):
+            _lib.check(status)
+
+
 # ----------------------------------------------------------------------------- the cases table
 def test_cases_select_the_configuration_they_name():
     """``launch_deskew``'s rule, restated, over the natural-selection geometries: the named configuration without a fill and with

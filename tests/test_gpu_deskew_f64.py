@@ -128,6 +128,28 @@ def test_deskew_oversized_tile_is_refused(gpu, monkeypatch):
     check("after the refusal", got, (shape, angle, ratio, N, True), 0)
 
 
+def test_deskew_unknown_dtype_code_is_refused(gpu, monkeypatch):
+    """A dtype code that is none of the four, without a fill and with a mean fill: BH_ERR_INVALID and the message naming the
+    code, nothing is launched (the output buffer keeps its marker), and the next valid call on the context is as good as before."""
+    from biahub_amd import _lib
+    from biahub_amd.deskew import get_deskewed_data_shape
+    from biahub_amd.device import get_context, ptr
+
+    shape, angle, ratio, N, keep, _ = D.EDGES[0]
+    vol = _input(shape, "f32", False)[0]
+    out = torch.full(get_deskewed_data_shape(shape, angle, ratio, keep, N)[0], -7.0, dtype=torch.float32, device=gpu)
+    ctx = get_context(gpu)
+    for mode in (_lib.FILL_NONE, _lib.FILL_MEAN):
+        with torch.cuda.device(gpu):
+            status = ctx.lib.bh_deskew(ctx.handle, ptr(vol), 99, *shape, angle, ratio, int(keep), N, mode, 0.0, ptr(out), None)
+        assert status == _lib.BH_ERR_INVALID and _lib.last_error() == "unsupported input dtype code 99", mode
+        torch.cuda.synchronize(gpu)
+        assert bool((out == -7.0).all()), mode
+    for fill in (0, "mean"):
+        got, _ = run(gpu, monkeypatch, (shape, angle, ratio, N, keep), fill)
+        check("after the refusal", got, (shape, angle, ratio, N, keep), fill)
+
+
 # ----------------------------------------------------------------------------- the persistent kernel
 PERS_MODES = {
     # what: (fill, switches of the persistent run, switches of the tile-kernel run, expected fill path)
@@ -151,7 +173,8 @@ def _assert_walk(gpu, shape, angle, ratio, N, ntiles):
 def test_deskew_persistent_walk_vs_float64(gpu, monkeypatch, shape, angle, ratio, N, ntiles, mode):
     """Three and more tiles per workgroup, a good part of them overhang: the persistent kernel without a fill, as the mask
     prologue and in its one-pass form — against float64, and bit-identical to the tile kernel outside the fill.
-    ``ntiles >= 3 x multi_processor_count`` is asserted at (48, 400, 128), (24, 576, 128) and (24, 575, 128).  (24, 402, 128) and
+    ``ntiles >= 3 x multi_processor_count`` is asserted at (48, 400, 128), (24, 576, 128), (24, 575, 128) and the N = 2 and N = 4
+    rows.  (24, 402, 128) and
     (24, 401, 128) have 536 tiles, fewer than 3 x 256: a workgroup walks ``ceil(ntiles / grid)`` = 3 consecutive tiles there (the
     179 workgroups that get any), which is what ``_assert_walk`` holds them to — deliberately, not by oversight."""
     _assert_walk(gpu, shape, angle, ratio, N, ntiles)

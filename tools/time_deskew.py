@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Deskew + fill passes alone at the bench shape (HIP-event times of the library's own timers, fifth of five runs).
-BHCORE_LIB=<variant .so> / BH_DESKEW_PERS=0 select what runs: tools/build_variant.py NAME --src=deskew.hip -D..."""
+BHCORE_LIB=<another build's libbhcore.so> and the run-time switches BH_DESKEW_CFG / BH_DESKEW_PERS / BH_DESKEW_ONEPASS /
+BH_DESKEW_ROWS_KERNEL select what runs (csrc/deskew.hip has no compile-time variants)."""
 import sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
