@@ -106,6 +106,7 @@ SIGNATURES = {
     "bh_affine": (_int, [_vp, _vp, _int, _i64, _i64, _i64, C.POINTER(_f64), _int, _int, _f32, _vp, _i64, _i64,
                          _i64, C.POINTER(_i64)]),
     "bh_spline_prefilter": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp]),
+    "bh_spline_path": (_int, [_vp, C.POINTER(_int)]),
     "bh_crop_flip": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, C.POINTER(_i64), _i64, _i64, _i64, _int,
                             _int, _int, _vp]),
     "bh_last_elapsed_ms": (_int, [_vp, _int, C.POINTER(_f32)]),

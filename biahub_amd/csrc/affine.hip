@@ -773,6 +773,7 @@ extern "C" int bh_affine(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, 
     using namespace bh;
     BH_REQUIRE(ctx && in && out && matrix, "NULL argument");
     ctx->affine_path = -1;  // a call that is refused below launched nothing
+    ctx->spline_path = -1;
     BH_REQUIRE(Zi > 0 && Yi > 0 && Xi > 0 && Zo > 0 && Yo > 0 && Xo > 0, "invalid shape");
     BH_REQUIRE(Zi < (1ll << 30) && Yi < (1ll << 30) && Xi < (1ll << 30) && Zo < (1ll << 30) && Yo < (1ll << 30) &&
                    Xo < (1ll << 30),

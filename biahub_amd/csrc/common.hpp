@@ -91,6 +91,10 @@ struct bh_ctx {
     int num_cus = 256;
     int deskew_path = 0;     // how the last bh_deskew filled the overhang: 0 mask pipeline (or no fill), 1 one-pass (deskew_rows.inc)
     int affine_path = -1;    // the launch of the last bh_affine: 0 staged tiles, 1 compact blocks, 2 z walk, 3 oblique walk, 4 cubic
+    // the launches of the last cubic bh_affine (or bh_spline_prefilter alone: bit 128 only), -1 like affine_path: 1 global gather,
+    // 2 tiles of 8 planes, 4 tiles of 4 planes; for tiles 8 plane combining (ZUNI), 16 quad staging, 32 pitch of 32 words, 64 512
+    // threads; 128 the x pass's VEC form
+    int spline_path = -1;
     int plans_replaced = 0;  // 3-D library plans that failed their self-check and were rebuilt decomposed (context.hip)
     // One-shot Richardson-Lucy on the engine box: the handle of the last call, its transfer function in scratch "fc_otf" /
     // "fc_otf_real" (not owned), built from the PSF kept in "rl_psf_kept" (compared byte for byte on every call).  Whoever

@@ -29,6 +29,9 @@ namespace bh {
 
 namespace sp {
 
+// bits of bh_spline_path
+constexpr int SP_GLOBAL = 1, SP_TILE8 = 2, SP_TILE4 = 4, SP_ZUNI = 8, SP_X4 = 16, SP_PAD32 = 32, SP_NT512 = 64, SP_VEC = 128;
+
 constexpr int R = 20;                             // run-in samples (truncation z^R = 3.6e-12)
 constexpr float Zp = -0.26794919243112270647f;    // sqrt(3) - 2
 constexpr float GAIN = 6.0f;                      // (1 - z)(1 - 1/z)
@@ -253,6 +256,43 @@ __device__ __forceinline__ float blend64(const float (&wz)[4], const float (&wy)
     return acc.x + acc.y;
 }
 
+// The same 64 taps in the order of the plane-combining path: the four z taps of every (y, x) tap first, by the fma chain that
+// combines the planes in place, then blend16's 4 x 4 blend — bit for bit what a voxel of a combined plane gets.  Every voxel of
+// a ZUNI launch that is not on a combined plane takes this order (z-edge tiles, voxels that fall back to global memory), so
+// the result of a launch does not depend on where its tile grid starts: a cropped output equals that part of the whole.
+template <typename RowFn>
+__device__ __forceinline__ float blend64_zfirst(const float (&wz)[4], const float (&wy)[4], const float (&wx)[4], const int (&ix)[4],
+                                                RowFn row) {
+    f2 ta[4][4], tb[4][4];
+#pragma unroll
+    for (int dz = 0; dz < 4; ++dz)
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy) {
+            const float* rowp = row(dz, dy);
+            ta[dz][dy] = f2{rowp[ix[0]], rowp[ix[1]]};
+            tb[dz][dy] = f2{rowp[ix[2]], rowp[ix[3]]};
+        }
+    __builtin_amdgcn_sched_barrier(0);
+    const f2 w0 = {wz[0], wz[0]}, w1 = {wz[1], wz[1]}, w2 = {wz[2], wz[2]}, w3 = {wz[3], wz[3]};
+    const f2 wa = {wx[0], wx[1]}, wb = {wx[2], wx[3]};
+    f2 az = {0.0f, 0.0f};
+#pragma unroll
+    for (int dy = 0; dy < 4; ++dy) {
+        const f2 ca = __builtin_elementwise_fma(w3, ta[3][dy], __builtin_elementwise_fma(w2, ta[2][dy], __builtin_elementwise_fma(w1, ta[1][dy], w0 * ta[0][dy])));
+        const f2 cb = __builtin_elementwise_fma(w3, tb[3][dy], __builtin_elementwise_fma(w2, tb[2][dy], __builtin_elementwise_fma(w1, tb[1][dy], w0 * tb[0][dy])));
+        const f2 ax = __builtin_elementwise_fma(cb, wb, ca * wa);
+        const f2 w = {wy[dy], wy[dy]};
+        az = dy == 0 ? ax * w : __builtin_elementwise_fma(ax, w, az);
+    }
+    return az.x + az.y;
+}
+
+template <bool ZFIRST, typename RowFn>
+__device__ __forceinline__ float blend64_as(const float (&wz)[4], const float (&wy)[4], const float (&wx)[4], const int (&ix)[4], RowFn row) {
+    if (ZFIRST) return blend64_zfirst(wz, wy, wx, ix, row);
+    return blend64(wz, wy, wx, ix, row);
+}
+
 // The 4 x 4 blend of one voxel on a plane whose z taps were combined beforehand (gather_tile_kernel<.., ZUNI>): 8 two-word
 // LDS reads, 13 packed operations.  row(dy) -> the plane's row of tap iy[dy]; ix[] the four x indices within it.
 template <typename RowFn>
@@ -276,6 +316,7 @@ __device__ __forceinline__ float blend16(const float (&wy)[4], const float (&wx)
 }
 
 // One voxel whose taps come through the vector cache (the fallback of the tile kernel, and the whole of gather_kernel).
+template <bool ZFIRST = false>
 __device__ __forceinline__ float sample_global(const float* __restrict__ coef, const GatherParams& p, double c0, double c1, double c2) {
     // SciPy "constant": a coordinate outside [0, n - 1] gives cval (no interpolation past the edge samples)
     if (!(c0 >= 0.0 && c0 <= (double)(p.Zi - 1) && c1 >= 0.0 && c1 <= (double)(p.Yi - 1) && c2 >= 0.0 && c2 <= (double)(p.Xi - 1)))
@@ -294,7 +335,7 @@ __device__ __forceinline__ float sample_global(const float* __restrict__ coef, c
         iy[k] = yin ? by + k : mirror(by + k, p.Yi);
         iz[k] = zin ? bz + k : mirror(bz + k, p.Zi);
     }
-    return blend64(wz, wy, wx, ix, [&](int dz, int dy) { return coef + ((long)iz[dz] * p.Yi + iy[dy]) * p.Xi; });
+    return blend64_as<ZFIRST>(wz, wy, wx, ix, [&](int dz, int dy) { return coef + ((long)iz[dz] * p.Yi + iy[dy]) * p.Xi; });
 }
 
 // One output voxel per thread, 8 x 8 x 4 voxel blocks per workgroup (x fastest), every tap through the vector cache: the
@@ -309,7 +350,7 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ c
     const double c0 = p.m[0] * gz + p.m[1] * gy + p.m[2] * gx + p.m[3];
     const double c1 = p.m[4] * gz + p.m[5] * gy + p.m[6] * gx + p.m[7];
     const double c2 = p.m[8] * gz + p.m[9] * gy + p.m[10] * gx + p.m[11];
-    out[((long)oz * p.Yo + oy) * p.Xo + ox] = sample_global(coef, p, c0, c1, c2);
+    out[((long)oz * p.Yo + oy) * p.Xo + ox] = sample_global<false>(coef, p, c0, c1, c2);
 }
 
 // ---- interpolation from LDS: a workgroup owns an 8 x 8 x 64 (z, y, x) output tile -------------------------------------------
@@ -441,7 +482,8 @@ __global__ __launch_bounds__(G_NT) void gather_tile_kernel(const float* __restri
         // vector instructions.  The combined planes replace the box IN PLACE, without a barrier between planes: a thread owns
         // 16-B columns of the box and walks the output planes upwards; with m00 >= 1 the first source plane b_k of output plane
         // k grows strictly, so plane b_k is read by no later output plane and takes the combination of k.  (z-interior tiles
-        // only: no mirrored planes, every plane in range; the other tiles, and matrices that compress z, take the 64-tap path.)
+        // only: no mirrored planes, every plane in range; the other tiles of such a launch blend 64 taps per voxel in the same
+        // order, blend64_zfirst; matrices that compress z take the 64-tap path.)
         for (int q = threadIdx.x; q < (pz >> 2); q += G_NT) {
             float4* col = reinterpret_cast<float4*>(tile) + q;
             const int pq = pz >> 2;
@@ -501,7 +543,7 @@ __global__ __launch_bounds__(G_NT) void gather_tile_kernel(const float* __restri
                 if (inbox)
                     v = blend16(wy, wx, ix, [&](int ky) { return buf + iy[ky] * P; });
                 else
-                    v = sample_global(coef, p, c0, c1, c2);
+                    v = sample_global<true>(coef, p, c0, c1, c2);
             }
             out[((long)oz * p.Yo + oy) * p.Xo + ox] = v;
         }
@@ -525,7 +567,7 @@ __global__ __launch_bounds__(G_NT) void gather_tile_kernel(const float* __restri
             weights3(c2, bx, wx);
             const float* q = tile + ((bz - bz0) * dy + (by - by0)) * P + (bx - bx0);
             const int ix[4] = {0, 1, 2, 3};
-            v = blend64(wz, wy, wx, ix, [&](int kz, int ky) { return q + kz * pz + ky * P; });
+            v = blend64_as<ZUNI>(wz, wy, wx, ix, [&](int kz, int ky) { return q + kz * pz + ky * P; });
         } else if (!(c0 >= 0.0 && c0 <= (double)(p.Zi - 1) && c1 >= 0.0 && c1 <= (double)(p.Yi - 1) && c2 >= 0.0 &&
                      c2 <= (double)(p.Xi - 1))) {
             v = p.cval;
@@ -545,9 +587,9 @@ __global__ __launch_bounds__(G_NT) void gather_tile_kernel(const float* __restri
                 inbox = inbox && (unsigned)ix[k] < (unsigned)dx && (unsigned)iy[k] < (unsigned)dy && (unsigned)iz[k] < (unsigned)dz;
             }
             if (inbox)
-                v = blend64(wz, wy, wx, ix, [&](int kz, int ky) { return tile + iz[kz] * pz + iy[ky] * P; });
+                v = blend64_as<ZUNI>(wz, wy, wx, ix, [&](int kz, int ky) { return tile + iz[kz] * pz + iy[ky] * P; });
             else
-                v = sample_global(coef, p, c0, c1, c2);
+                v = sample_global<ZUNI>(coef, p, c0, c1, c2);
         }
         out[((long)oz * p.Yo + oy) * p.Xo + ox] = v;
     }
@@ -577,6 +619,7 @@ static int prefilter_typed(bh_ctx* ctx, const TIN* in, int64_t Z, int64_t Y, int
     hipStream_t s = ctx->stream;
     const long rows = Z * Y, n = rows * X;
     constexpr int B = 64;
+    bool vec = false;
     // x: in -> coef
     if (X > 1) {
         const int clen = (int)std::min<int64_t>(X, XCH), nchunk = (int)ceil_div(X, XCH);
@@ -589,7 +632,7 @@ static int prefilter_typed(bh_ctx* ctx, const TIN* in, int64_t Z, int64_t Y, int
         const long nunits = rows * nchunk;
         const long grid = ceil_div(nunits, rpw);
         BH_REQUIRE(grid < (1ll << 31), "volume too large for the spline prefilter");
-        const bool vec = X % 4 == 0 && reinterpret_cast<uintptr_t>(in) % (4 * sizeof(TIN)) == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0;
+        vec = X % 4 == 0 && reinterpret_cast<uintptr_t>(in) % (4 * sizeof(TIN)) == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0;
         auto kern = vec ? x_kernel<TIN, true> : x_kernel<TIN, false>;
         if (lds > 64 * 1024)
             BH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -617,6 +660,7 @@ static int prefilter_typed(bh_ctx* ctx, const TIN* in, int64_t Z, int64_t Y, int
     BH_TRY(axis((int)Z, (long)Y * X, X, (int)Y));  // z: columns (y, x)
     if (a != coef) BH_CHECK_HIP(hipMemcpyAsync(coef, a, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
     BH_CHECK_HIP(hipGetLastError());
+    ctx->spline_path = vec ? SP_VEC : 0;
     return BH_OK;
 }
 
@@ -641,6 +685,8 @@ int affine_cubic(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, int64_t 
     float* coef = nullptr;
     BH_TRY(get_scratch(ctx, "spline_coef", (size_t)Zi * Yi * Xi * sizeof(float), (void**)&coef));
     BH_TRY(sp::prefilter(ctx, in, in_dtype, Zi, Yi, Xi, coef));
+    int report = ctx->spline_path;  // the x pass's form; the gather's bits join it once the launch is made
+    ctx->spline_path = -1;
     sp::GatherParams p;
     for (int i = 0; i < 12; ++i) p.m[i] = matrix[i];
     p.Zi = (int)Zi;
@@ -685,12 +731,16 @@ int affine_cubic(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, int64_t 
             BH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)(per_xcd * 8)), dim3(nt == 512 ? 512 : 256), lds, ctx->stream, coef, out, p, (int)ntx, (int)nty,
                            (int)ntiles, per_xcd, lds_floats, x4 ? 1 : 0, pad32 ? 1 : 0);
+        report |= (gtz == 8 ? sp::SP_TILE8 : sp::SP_TILE4) | (zuni ? sp::SP_ZUNI : 0) | (x4 ? sp::SP_X4 : 0) | (pad32 ? sp::SP_PAD32 : 0) |
+                  (nt == 512 ? sp::SP_NT512 : 0);
     } else {
         const dim3 grid((unsigned)ceil_div(Xo, 8), (unsigned)ceil_div(Yo, 8), (unsigned)ceil_div(Zo, 4));
         BH_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "affine output too large");
         hipLaunchKernelGGL(sp::gather_kernel, grid, dim3(256), 0, ctx->stream, coef, out, p);
+        report |= sp::SP_GLOBAL;
     }
     BH_CHECK_HIP(hipGetLastError());
+    ctx->spline_path = report;
     return BH_OK;
 }
 
@@ -698,8 +748,15 @@ int affine_cubic(bh_ctx* ctx, const void* in, int in_dtype, int64_t Zi, int64_t 
 
 extern "C" int bh_spline_prefilter(bh_ctx* ctx, const void* in, int in_dtype, int64_t Z, int64_t Y, int64_t X, float* coef) {
     BH_REQUIRE(ctx && in && coef, "NULL argument");
+    ctx->spline_path = -1;
     BH_REQUIRE(Z > 0 && Y > 0 && X > 0 && Z < (1ll << 30) && Y < (1ll << 30) && X < (1ll << 30), "invalid shape");
     BH_REQUIRE((const void*)coef != in, "the prefilter runs out of place");
     BH_CHECK_HIP(hipSetDevice(ctx->device));
     return bh::sp::prefilter(ctx, in, in_dtype, Z, Y, X, coef);
+}
+
+extern "C" int bh_spline_path(bh_ctx* ctx, int* code) {
+    BH_REQUIRE(ctx != nullptr && code != nullptr, "NULL argument");
+    *code = ctx->spline_path;
+    return BH_OK;
 }

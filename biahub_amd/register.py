@@ -104,6 +104,21 @@ def affine_path(device=None) -> int:
     return int(path.value)
 
 
+SPLINE_GLOBAL, SPLINE_TILE8, SPLINE_TILE4, SPLINE_ZUNI, SPLINE_X4, SPLINE_PAD32, SPLINE_NT512, SPLINE_VEC = (1 << k for k in range(8))
+
+
+def spline_path(device=None) -> int:
+    """The launches of the last cubic ``affine_device`` on ``device`` as bits (diagnostic): the gather through the cache, LDS tiles
+    of 8 or of 4 output planes; with tiles the z planes combined per output plane, 16-byte staging, the 32-word row pitch and 512
+    threads; and the prefilter's x pass in its 4-sample form (the only bit a bare ``bh_spline_prefilter`` sets).  -1 before the first
+    call, after a linear or nearest warp and after a call that was refused."""
+    dev = resolve_device(device if device is not None else "cuda")
+    ctx = get_context(dev)
+    code = C.c_int(-1)
+    _lib.check(ctx.lib.bh_spline_path(ctx.handle, C.byref(code)))
+    return int(code.value)
+
+
 def cast_like_scipy(t: torch.Tensor, dtype) -> torch.Tensor:
     """SciPy's conversion of an interpolated value into the output dtype (ni_interpolation.c, CASE_INTERP_OUT_*): floating
     types are cast; integers round half away from zero (unsigned: negatives -> 0) and saturate at the type's range."""

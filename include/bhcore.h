@@ -445,6 +445,12 @@ int bh_affine_path(bh_ctx* ctx, int* path);
  * B-spline with mirror boundaries; axes of length 1 are left alone; NaN inputs read as 0.  in: (Z,Y,X) of in_dtype;
  * coef: float32 (Z,Y,X), distinct from in.  bh_affine(BH_INTERP_CUBIC) runs this into the context's scratch itself. */
 int bh_spline_prefilter(bh_ctx* ctx, const void* in, int in_dtype, int64_t Z, int64_t Y, int64_t X, float* coef);
+/* Diagnostic (host only, does not synchronise): the launches of the last cubic bh_affine of this context as bits — 1 the
+ * gather with every tap through the cache, 2 LDS tiles of 8 output planes, 4 LDS tiles of 4; with tiles 8 the four z planes
+ * combined once per output plane, 16 16-byte staging, 32 an LDS row pitch of 32 words, 64 workgroups of 512 threads; 128 the
+ * prefilter's x pass in its 4-sample form.  After bh_spline_prefilter alone: 0 or 128.  -1 before the first call, on entry to
+ * every bh_affine (so after a linear or nearest one too) and after a call that was refused. */
+int bh_spline_path(bh_ctx* ctx, int* code);
 
 /* ---- bit-exact crop / flip --------------------------------------------------------- */
 /* (C, Zi, Yi, Xi) of itemsize bytes -> (C, Zo, Yo, Xo) starting at lo, optionally flipped along

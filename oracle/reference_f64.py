@@ -22,6 +22,10 @@ with their float32 weights, every tap, product and sum in float64, and the magni
 Affine warp (``oracle_np.affine_pull``, orders 0 and 1):  the inside rule on the float64 coordinate; linear with an edge clamp at
 the operator's Q32.32 sample positions (exact integers), every tap, weight and sum in float64; ZEROS and nearest at the float64
 positions; and the largest tap magnitude beside it.
+Cubic B-spline warp (``oracle_np.spline_prefilter`` / ``spline_affine_pull``, SciPy order 3, mode "constant"):  the coefficients by
+SciPy's recursion with its exact mirror initialisation, the 4^n taps mirrored about the edge samples with SciPy's float64 weight
+polynomials, and beside the value the local scale M = sum_i w_i A[tap_i], A the samples' magnitudes under the absolute value of
+the prefilter's impulse response.
 
 Inputs may be numpy arrays or torch tensors; results are float64 torch tensors on the input's device (or ``device``).
 Nothing here imports the product package.
@@ -450,3 +454,168 @@ def warp_f64(vol, matrix, output_shape, crop_lo=(0, 0, 0), interpolation="linear
     V = torch.where(inside, V, cvt)
     M = torch.where(inside, M, cvt.abs())
     return V, M, inside
+
+
+# ----------------------------------------------------------------------------- cubic B-spline warp
+SPLINE_POLE = float(np.sqrt(3.0) - 2.0)
+SPLINE_REACH = 128      # |k| <= 128 of the impulse response: |z|^128 = 6e-74 of a sample, beyond what any kernel block can see
+
+
+def _clean_f64(vol, device=None) -> torch.Tensor:
+    """``nan_to_num(nan=0)`` in the input's own type (NaN -> 0, +-inf -> +-FLT_MAX for float32), widened exactly."""
+    if isinstance(vol, np.ndarray) and not vol.flags.writeable:
+        vol = vol.copy()
+    x = _tensor(vol, device)
+    if x.dtype == torch.uint16:
+        x = x.to(torch.int32)
+    if x.is_floating_point():
+        x = torch.nan_to_num(x, nan=0.0)
+    return x.to(F64)
+
+
+def mirror_index(i: torch.Tensor, n: int) -> torch.Tensor:
+    """Whole-sample symmetric extension of 0 .. n - 1 to any integer i (n == 1: always 0)."""
+    if n <= 1:
+        return torch.zeros_like(i)
+    s2 = 2 * n - 2
+    i = torch.remainder(i, s2)
+    return torch.where(i >= n, s2 - i, i)
+
+
+def spline_coef_f64(vol, device=None) -> torch.Tensor:
+    """float64 cubic B-spline coefficients of an n-D array, axis by axis as SciPy computes them (ni_splines.c): c = 6 s; the causal
+    start value c[0] = (sum_{i=0}^{n-2} z^i (c[i] + z^(n-1) c[n-1-i])) / (1 - z^(2n-2)) — the exact sum over the mirror extension,
+    no run-in —; c[i] += z c[i-1]; c[n-1] = z (z c[n-2] + c[n-1]) / (z^2 - 1); c[i] = z (c[i+1] - c[i]).  Axes of length 1 are left
+    alone.  The input is cleaned first (``nan_to_num(nan=0)``)."""
+    c = _clean_f64(vol, device)
+    z = SPLINE_POLE
+    for ax in range(c.ndim):
+        n = int(c.shape[ax])
+        if n <= 1:
+            continue
+        c = (c.movedim(ax, 0) * ((1.0 - z) * (1.0 - 1.0 / z))).contiguous()
+        zn1 = z ** (n - 1)
+        shape = (-1,) + (1,) * (c.ndim - 1)
+        zi = torch.from_numpy(z ** np.arange(n - 1, dtype=np.float64)).to(c.device).reshape(shape)      # z^0 .. z^(n-2)
+        c0 = (zi * c[: n - 1]).sum(0) + zn1 * c[n - 1]
+        if n > 2:
+            c0 = c0 + zn1 * (zi[1:] * c[1: n - 1].flip(0)).sum(0)      # i = 1 .. n-2: z^i z^(n-1) c[n-1-i]
+        c[0] = c0 / (1.0 - zn1 * zn1)
+        for i in range(1, n):
+            c[i] += z * c[i - 1]
+        c[n - 1] = (z * c[n - 2] + c[n - 1]) * z / (z * z - 1.0)
+        for i in range(n - 2, -1, -1):
+            c[i] = z * (c[i + 1] - c[i])
+        c = c.movedim(0, ax)
+    return c.contiguous()
+
+
+def spline_scale_f64(vol, device=None, weight=None) -> torch.Tensor:
+    """A: the mirror-extended |sample| convolved per axis (length > 1) with ``sqrt(3) |z|^|k|``, the absolute value of the
+    prefilter's impulse response (row sum 3): |coefficient| <= A everywhere, and A is local — a sample k voxels away along an axis
+    counts with 0.268^|k|.  ``weight(k, axis)`` (an array over k = -REACH .. REACH) replaces the kernel on the axes it returns
+    something for: tests/cubic_cases.py convolves with its rounding-error kernels that way."""
+    a = _clean_f64(vol, device).abs()
+    K = SPLINE_REACH
+    k = np.arange(-K, K + 1)
+    for ax in range(a.ndim):
+        n = int(a.shape[ax])
+        if n <= 1:
+            continue
+        h = None if weight is None else weight(k, ax)
+        if h is None:
+            h = np.sqrt(3.0) * np.abs(SPLINE_POLE) ** np.abs(k)
+        idx = mirror_index(torch.arange(-K, n + K, device=a.device), n)
+        ext = a.index_select(ax, idx)
+        out = torch.zeros_like(a)
+        for j, hj in enumerate(h):
+            if hj != 0.0:
+                out += float(hj) * ext.narrow(ax, j, n)
+        a = out
+    return a
+
+
+def spline3_weights_f64(x: torch.Tensor):
+    """SciPy's four cubic B-spline weights of the taps floor(c) - 1 .. floor(c) + 2 at the fraction x = c - floor(c), in float64."""
+    z = 1.0 - x
+    w1 = (x * x * (x - 2.0) * 3.0 + 4.0) / 6.0
+    w2 = (z * z * (z - 2.0) * 3.0 + 4.0) / 6.0
+    w0 = z * z * z / 6.0
+    return [w0, w1, w2, 1.0 - w0 - w1 - w2]
+
+
+def cubic_geometry_f64(in_shape, matrix, output_shape, crop_lo=None, device=None):
+    """(inside, idx, wts, frac) of the cubic warp: ``inside`` on the float64 coordinate in the association
+    ((m0 p0 + m1 p1) + m2 p2) + m3, p the integer output index plus crop_lo (SciPy "constant": 0 <= c <= n - 1 on every axis);
+    per axis the four mirrored tap indices (int64), SciPy's float64 weights and the fraction, each broadcastable to the output."""
+    nd = len(in_shape)
+    m = np.asarray(matrix, dtype=np.float64)[:nd, : nd + 1]
+    lo = (0,) * nd if crop_lo is None else crop_lo
+    g = []
+    for a in range(nd):
+        view = [1] * nd
+        view[a] = -1
+        g.append(torch.arange(int(lo[a]), int(lo[a]) + int(output_shape[a]), device=device, dtype=torch.int64).to(F64).reshape(view))
+    inside = torch.ones(tuple(int(n) for n in output_shape), dtype=torch.bool, device=device)
+    coords = []
+    for a in range(nd):
+        c = float(m[a, 0]) * g[0]
+        for b in range(1, nd):
+            c = c + float(m[a, b]) * g[b]
+        c = c + float(m[a, nd])
+        coords.append(c)
+        inside = inside & (c >= 0.0) & (c <= float(in_shape[a] - 1))
+    idx, wts, frac = [], [], []
+    for c, n in zip(coords, in_shape):
+        c = torch.where(inside, c, torch.zeros((), dtype=F64, device=device))
+        fl = torch.floor(c)
+        x = c - fl
+        base = fl.to(torch.int64) - 1
+        idx.append([mirror_index(base + k, int(n)) for k in range(4)])
+        wts.append(spline3_weights_f64(x))
+        frac.append(x)
+    return inside, idx, wts, frac
+
+
+def cubic_sum_f64(fields, idx, wts, weight_sets=None):
+    """sum over the 4^n taps of (prod_a wts[a][k_a]) field[idx[0][k_0], ...] in float64, for every field of the list (one tensor:
+    one result).  ``weight_sets``: further weight lists like ``wts`` — the result is then a list per weight set (wts first)."""
+    single = isinstance(fields, torch.Tensor)
+    fields = [fields] if single else list(fields)
+    sets = [wts] + list(weight_sets or [])
+    nd = fields[0].ndim
+    flats = [f.reshape(-1) for f in fields]
+    strides = [int(np.prod(fields[0].shape[a + 1:], dtype=np.int64)) for a in range(nd)]
+    offs = [[idx[a][k] * strides[a] for k in range(4)] for a in range(nd)]
+    acc = [[None] * len(fields) for _ in sets]
+    for taps in np.ndindex(*([4] * nd)):
+        off = offs[0][taps[0]]
+        for a in range(1, nd):
+            off = off + offs[a][taps[a]]
+        vals = [f[off] for f in flats]
+        for s, ws in enumerate(sets):
+            w = ws[0][taps[0]]
+            for a in range(1, nd):
+                w = w * ws[a][taps[a]]
+            for j, v in enumerate(vals):
+                acc[s][j] = w * v if acc[s][j] is None else acc[s][j] + w * v
+    out = [a[0] if single else a for a in acc]
+    return out[0] if weight_sets is None else out
+
+
+def cubic_warp_f64(vol, matrix, output_shape, crop_lo=None, cval=0.0, device=None):
+    """``scipy.ndimage.affine_transform(vol, matrix, output_shape=..., order=3, mode="constant", cval=cval)`` in float64, on the
+    sub-box starting at ``crop_lo`` of the output grid; n-D (2-D images, 3-D volumes).
+
+    * The input is cleaned first (``nan_to_num(nan=0)``), the coefficients are ``spline_coef_f64``.
+    * ``inside`` on the float64 coordinate (``cubic_geometry_f64``); outside it V is ``cval`` (rounded to float32 once).
+    * SciPy's float64 weight polynomials, taps mirrored about the edge samples, the float64 sum.
+
+    Returns ``(V, M, inside)``: M = sum_i w_i A[tap_i] with A = ``spline_scale_f64`` — the scale a float32 evaluation's rounding
+    error is measured in (``|cval|`` outside): local, unlike the volume's maximum."""
+    x = _clean_f64(vol, device)
+    dev = x.device
+    inside, idx, wts, _ = cubic_geometry_f64(tuple(x.shape), matrix, output_shape, crop_lo, dev)
+    V, M = cubic_sum_f64([spline_coef_f64(x), spline_scale_f64(x)], idx, wts)
+    cv = torch.full((), float(np.float32(cval)), dtype=F64, device=dev)
+    return torch.where(inside, V, cv), torch.where(inside, M, cv.abs()), inside
