@@ -19,6 +19,8 @@ Smooth + shrink (``oracle_np.smooth_shrink``):  per axis out[i] = sum_k w[k] in[
 float32 as ``bh_smooth_shrink`` stages them, every sum in float64.
 Deskew (``oracle_np.fast_deskew_zyx``):  (1/N) sum_k (v0 w0 + v1 w1) at the float32 sample positions of ``oracle_np.deskew_coords``
 with their float32 weights, every tap, product and sum in float64, and the magnitude sum beside it; then the reference's fill.
+Overhang fill (``oracle_np.fill_overhang`` / ``fill_overhang_with_mean``):  mask = (vol == 0) dilated by the 3x3x3 cube or the cross,
+the float64 mean of the rest, and the magnitude per valid voxel that a sum(all) - sum(masked) evaluation carries.
 Affine warp (``oracle_np.affine_pull``, orders 0 and 1):  the inside rule on the float64 coordinate; linear with an edge clamp at
 the operator's Q32.32 sample positions (exact integers), every tap, weight and sum in float64; ZEROS and nearest at the float64
 positions; and the largest tap magnitude beside it.
@@ -304,6 +306,49 @@ def dilate_mask(mask: torch.Tensor, iterations: int = 3) -> torch.Tensor:
             grown.narrow(axis, 0, m.shape[axis] - 1).logical_or_(hi)
             m = grown
     return m
+
+
+def dilate_mask_cross(mask: torch.Tensor, iterations: int = 3) -> torch.Tensor:
+    """The 6-connected counterpart of ``dilate_mask`` (SciPy ``binary_dilation``'s default structure, border value 0):
+    ``iterations`` steps of m | (m shifted by +-1 along each axis), every shift of a step taken from the previous step's m, nothing
+    entering from outside the array — the L1 ball of radius ``iterations``."""
+    m = mask.clone()
+    for _ in range(int(iterations)):
+        grown = m.clone()
+        for axis in range(3):
+            n = m.shape[axis]
+            if n > 1:
+                grown.narrow(axis, 1, n - 1).logical_or_(m.narrow(axis, 0, n - 1))
+                grown.narrow(axis, 0, n - 1).logical_or_(m.narrow(axis, 1, n - 1))
+        m = grown
+    return m
+
+
+def fill_overhang_f64(vol, fill_value=None, iterations: int = 3, connectivity: int = 26, device=None):
+    """``oracle_np.fill_overhang`` (connectivity 26) / ``fill_overhang_with_mean`` (6) with the mean in float64: ``(mask, fill, kappa)``.
+
+      mask   ``vol == 0`` (so -0.0 too; a subnormal is not zero) dilated ``iterations`` times by the 3x3x3 cube or the cross;
+      fill   the float64 mean of ``vol[~mask]`` (NaN when nothing is outside the mask), or ``fill_value`` as a float;
+      kappa  (sum |vol| + sum |vol[mask]|) / count(~mask): the magnitude that the two float64 sums of csrc/fill.hip — over all
+             voxels and over the masked ones — carry per valid voxel; the rounding bound of tests/fill_cases.py scales with it
+             (infinite when nothing is outside the mask).
+    The filled volume is ``torch.where(mask, fill, vol)``."""
+    if isinstance(vol, np.ndarray) and not vol.flags.writeable:
+        vol = vol.copy()
+    x = _tensor(vol, device)
+    if x.ndim != 3:
+        raise ValueError(f"vol must be 3-D (Z, Y, X), got {tuple(x.shape)}")
+    if connectivity not in (6, 26):
+        raise ValueError(f"connectivity must be 6 or 26, got {connectivity}")
+    mask = (dilate_mask if connectivity == 26 else dilate_mask_cross)(x == 0, iterations)
+    nvalid = x.numel() - int(mask.sum())
+    x64 = x.to(F64)
+    if fill_value is None:
+        fill = float(x64[~mask].sum()) / nvalid if nvalid else float("nan")
+    else:
+        fill = float(fill_value)
+    mag = float(x64.abs().sum()) + float(x64[mask].abs().sum())
+    return mask, fill, (mag / nvalid if nvalid else float("inf"))
 
 
 def deskew_f64(raw, ls_angle_deg, px_to_scan_ratio, keep_overhang, average_n_slices=1, overhang_fill=0, device=None):

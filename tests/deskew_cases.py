@@ -200,6 +200,14 @@ def selected_cfg(shape, angle, ratio, N, one_pass=False, keep_overhang=True):
     return pick, lds[pick]
 
 
+def tile_workgroups(shape, angle, ratio, N, cfg, keep_overhang=True):
+    """launch_deskew_cfg's grid for configuration ``cfg``: ceil(X / TX) x ceil(Xp / (64 J)) x Za workgroups.  With the mask prologue
+    each of them hands ``finalize_kernel`` (csrc/fill.hip) one block sum."""
+    TX, J = CANDIDATES[cfg]
+    Za, Xp = geometry(shape, angle, ratio, N, keep_overhang)[:2]
+    return -(-shape[2] // TX) * -(-Xp // (64 * J)) * Za
+
+
 def persistent(shape, angle, ratio, N, keep_overhang=True):
     """launch_deskew_pers for float32 input: None when the kernel declines (N > 4, X no multiple of 64, two tile buffers above
     160 KiB), else (ntiles, tiles whose window lies outside the volume, LDS bytes)."""
