@@ -15,7 +15,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "libbhcore.so"
 
 BH_OK, BH_ERR_INVALID, BH_ERR_HIP, BH_ERR_NOMEM, BH_ERR_UNSUPPORTED = range(5)
-DT_U8, DT_U16, DT_F32, DT_I16 = 0, 1, 2, 3
+DT_U8, DT_U16, DT_F32, DT_I16, DT_F16 = 0, 1, 2, 3, 4  # DT_F16: only as out_dtype of bh_stitch_blend
 FILL_NONE, FILL_CONSTANT, FILL_MEAN = 0, 1, 2
 INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC = 0, 1, 3
 BOUNDARY_ITK, BOUNDARY_SCIPY_CONSTANT, BOUNDARY_ZEROS = 0, 1, 2
@@ -46,6 +46,10 @@ SIGNATURES = {
     "bh_bin_reduce": (_int, [_vp, _vp, _int, _i64, _i64, _i64, C.POINTER(_int), _int, _vp, C.POINTER(_f32)]),
     "bh_bin_finish": (_int, [_vp, _vp, _i64, _int, _f32, _f32, _f32, _int, _vp]),
     "bh_pyramid_downsample": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _int, _int, C.POINTER(_vp)]),
+    "bh_stitch_blend": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_i64), _int, _i64, _i64, _i64, _f64, C.POINTER(_i64), C.POINTER(_i64),
+                               _int, _vp]),
+    "bh_stitch_tile_lists": (_int, [_int, C.POINTER(_i64), _i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64, C.POINTER(_i64)]),
     "bh_valid_mask": (_int, [_vp, _vp, _int, _i64, _vp, C.POINTER(C.c_uint64)]),
     "bh_bits_and": (_int, [_vp, _vp, _vp, _i64]),
     "bh_bits_unpack": (_int, [_vp, _vp, _i64, _vp]),

@@ -20,7 +20,7 @@ from .io import create_empty_plate, open_ome_zarr, process_single_position
 from .settings import (DeconvolveSettings, DeskewSettings, EstimateRegistrationSettings,
                        EstimateStabilizationSettings, FlatFieldCorrectionSettings, PhaseCrossCorrSettings,
                        ProcessingImportFuncSettings, PsfFromBeadsSettings, RegistrationSettings, RichardsonLucySettings,
-                       StabilizationSettings)
+                       StabilizationSettings, StitchSettings)
 from .utils.cluster import echo_resources, estimate_resources, get_submitit_cluster
 from .utils.config import model_to_yaml, settings_fingerprint, yaml_to_model
 from .utils.paths import get_output_paths, sbatch_to_submitit
@@ -859,6 +859,112 @@ def pyramid_cli(input_position_dirpaths, sbatch_filepath, local, levels, method)
     log_parent = pos.parents[3] if len(pos.parents) > 3 else pos.parent  # next to the plate (row/col/fov below it)
     _run_positions("pyramid", input_position_dirpaths, input_position_dirpaths,
                    lambda src, dst: pyramid(src, levels=levels, method=method), log_parent)
+
+
+@cli.command("estimate-stitch")
+@click.option("--input-position-dirpaths", "-i", multiple=True, required=True, callback=_positions,
+              help='Paths to input positions, e.g. "input.zarr/*/*/*"')
+@click.option("--output-filepath", "-o", required=True, type=click.Path(path_type=Path), help="Path to the output YAML config")
+@click.option("--fliplr", is_flag=True, help="Flip images left-right before stitching")
+@click.option("--flipud", is_flag=True, help="Flip images up-down before stitching")
+@click.option("--flipxy", is_flag=True, help="Flip images along the diagonal before stitching")
+@click.option("--pcc-channel-name", default=None, type=str,
+              help="(phase cross-correlation refinement of the reference: not available here)")
+@click.option("--local", "-l", is_flag=True, default=False, help="Accepted for compatibility: this verb runs on the host.")
+@click.option("--monitor", "-m", is_flag=True, default=False, help="Accepted for compatibility.")
+def estimate_stitch_cli(input_position_dirpaths, output_filepath, fliplr, flipud, flipxy, pcc_channel_name, local, monitor):
+    """Estimate stitching translations, in pixels, from the plate's micro-manager stage positions and the scale metadata
+    (reference: ``biahub estimate-stitch`` without ``--pcc-channel-name``, estimate_stitch.py:16-64, 118-213).  Host only."""
+    from .io import _read_group_attrs
+    from .stitch import estimate_stitch_translations, extract_stage_position
+
+    if pcc_channel_name is not None:
+        raise click.UsageError("--pcc-channel-name (pairwise phase cross-correlation and the shift-graph optimiser) is not "
+                               "available in biahub_amd; use the reference biahub package for it.")
+    plate_path = Path(input_position_dirpaths[0]).parents[2]
+    plate_attrs = _read_group_attrs(plate_path)
+    click.echo("Reading stage positions...")
+    stage = {}
+    for p in input_position_dirpaths:
+        name = "/".join(Path(p).parts[-3:])
+        with open_ome_zarr(p) as pos:
+            label = pos.zattrs["omero"]["name"]
+        stage[name] = extract_stage_position(plate_attrs, label)
+        click.echo(f"Found metadata: {name}: {stage[name]}")
+    with open_ome_zarr(input_position_dirpaths[0]) as pos:
+        scale_zyx = pos.scale[2:]
+    translations = estimate_stitch_translations(stage, scale_zyx, fliplr=fliplr, flipud=flipud, flipxy=flipxy)
+    model_to_yaml(StitchSettings(channels=None, total_translation=translations), output_filepath)
+
+
+@cli.command("stitch")
+@click.option("--input-position-dirpaths", "-i", multiple=True, required=True, callback=_positions,
+              help='Paths to input positions, e.g. "input.zarr/*/*/*"')
+@_config
+@click.option("--output-dirpath", "-o", required=True, type=click.Path(path_type=Path), help="Path to output.zarr")
+@click.option("--sbatch-filepath", "-sb", default=None, type=click.Path(exists=True),
+              help="Accepted for compatibility; Slurm parameters are parsed and ignored.")
+@click.option("--local", "-l", is_flag=True, default=False, help="Accepted for compatibility: this build always runs in-process.")
+@click.option("--verbose", "-v", is_flag=True, help="Verbose stitching output.")
+@click.option("--blending-exponent", "-b", type=float, default=1.0, show_default=True,
+              help="Exponent for blending weights. 0.0 is average blending, 1.0 is linear blending, and >1.0 is progressively "
+                   "sharper S-curve blending.")
+@click.option("--monitor", "-m", is_flag=True, default=False, help="Accepted for compatibility.")
+def stitch_cli(input_position_dirpaths, config_filepath, output_dirpath, sbatch_filepath, local, verbose, blending_exponent, monitor):
+    """Stitch the FOVs of each well into one FOV ``row/col/0`` with the shifts of ``estimate-stitch``, blended on the GPU
+    (reference: ``biahub stitch``, stitch.py:314-496).  The output is float16 with chunks (1, 1, 10, y_chunk, x_chunk) of the input."""
+    import os
+
+    from .stitch import get_output_shape, placements, stitch_well
+
+    click.echo("Starting stitching...")
+    settings = yaml_to_model(config_filepath, StitchSettings)
+    if not settings.total_translation:
+        raise click.UsageError("the settings carry affine_transform but no total_translation: stitch places FOVs by "
+                               "total_translation only (as the reference does)")
+    if not blending_exponent >= 0:
+        raise click.UsageError(f"--blending-exponent {blending_exponent}: expected a value >= 0")
+    plate_path = Path(input_position_dirpaths[0]).parents[2]
+    with open_ome_zarr(input_position_dirpaths[0]) as first:
+        input_channels = first.channel_names
+        version = settings.output_ome_zarr_version or first.version
+    channels = settings.channels or input_channels
+    if not all(ch in input_channels for ch in channels):
+        raise click.UsageError(f"Invalid channel(s) provided: {channels} (the input has {input_channels})")
+    channel_idx = [input_channels.index(ch) for ch in channels]
+    wells: dict = {}
+    for key, value in settings.total_translation.items():
+        wells.setdefault("/".join(key.split("/")[:2]), {})[key] = value
+    jobs = {}
+    for well, shifts in wells.items():
+        try:
+            placements(shifts.values())
+        except ValueError as e:
+            raise click.UsageError(f"well {well}: {e}") from e
+        names = list(shifts)
+        for n in names:
+            if not (plate_path / n).is_dir():
+                raise click.UsageError(f"{plate_path / n}: no such position (named in total_translation)")
+        with open_ome_zarr(plate_path / names[0]) as fov:
+            shape, chunks, scale = fov.data.shape, fov.data.chunks, fov.scale
+        mosaic = get_output_shape(shifts, shape)
+        row, col = well.split("/")
+        _create_plate_once(output_dirpath, [(row, col, "0")], channels, (shape[0], len(channels), *mosaic),
+                           chunks=(1, 1, 10, chunks[-2], chunks[-1]), scale=scale, dtype=np.float16, version=version,
+                           compressor=_output_compressor())
+        jobs[well] = ([plate_path / n for n in names], list(shifts.values()), Path(output_dirpath) / row / col / "0")
+    _, cpus, gb = estimate_resources(shape, ram_multiplier=25, max_num_cpus=16)
+    echo_resources(cpus, cpus * gb, 60)
+    if sbatch_filepath:
+        sbatch_to_submitit(sbatch_filepath)
+    _resolve_cluster(None, local=True)
+    budget = int(os.environ["BH_STITCH_MAX_DEVICE_BYTES"]) if os.environ.get("BH_STITCH_MAX_DEVICE_BYTES") else None
+
+    def job(well, dst):
+        paths, shifts, _ = jobs[well]
+        stitch_well(paths, shifts, dst, channel_idx, blending_exponent=blending_exponent, max_device_bytes=budget, verbose=verbose)
+
+    _run_positions("stitch", list(jobs), [j[2] for j in jobs.values()], job, Path(output_dirpath).parent)
 
 
 def main(argv=None):

@@ -82,7 +82,8 @@ def _torch_dtype(dtype):
         import torch
 
         _TORCH_DT = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16, np.dtype(np.int16): torch.int16,
-                     np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32}
+                     np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
+                     np.dtype(np.float16): torch.float16}
     return _TORCH_DT.get(np.dtype(dtype))
 
 

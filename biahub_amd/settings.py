@@ -248,6 +248,38 @@ def _nonneg(r):
         raise ValueError("Slice indices must be non-negative integers.")
 
 
+class StitchSettings(_Strict):
+    """biahub/settings.py:653-674: shifts in pixels per FOV name ("row/col/fov"); two-element (y, x) translations get a leading
+    0; at least one of ``total_translation`` and ``affine_transform`` must be given (``stitch`` itself reads only
+    ``total_translation``)."""
+
+    channels: list[str] | None = None
+    total_translation: dict[str, list[float]] | None = None
+    affine_transform: dict[str, list] | None = None
+    output_ome_zarr_version: OmeZarrVersion | None = None
+
+    @model_validator(mode="before")
+    @classmethod
+    def _leading_zero(cls, data):
+        if not isinstance(data, dict):
+            return data
+        data = dict(data)
+        if isinstance(data.get("total_translation"), dict):
+            data["total_translation"] = {k: ([0] + list(v) if len(v) == 2 else list(v)) for k, v in data["total_translation"].items()}
+        if not (data.get("total_translation") or data.get("affine_transform")):
+            raise ValueError("Either affine_transform or total_translation must be provided")
+        return data
+
+    @field_validator("total_translation")
+    @classmethod
+    def _three(cls, v):
+        if v is not None:
+            for k, t in v.items():
+                if len(t) != 3:
+                    raise ValueError(f"total_translation[{k!r}]: expected (z, y, x) or (y, x), got {len(t)} values")
+        return v
+
+
 class ConcatenateSettings(_Strict):
     """`biahub/settings.py:452-620`: what to concatenate (glob per source), which channels, optional per-source crops,
     output chunking / sharding and NGFF version (0.5 by default: concatenate is the migration path into v3 stores)."""

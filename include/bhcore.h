@@ -12,6 +12,8 @@
  *   bh_bin_reduce, bh_bin_finish
  *                          <- biahub/process_data.py:29-105 binning_czyx
  *   bh_pyramid_downsample  <- biahub/pyramid.py:19-40 pyramid (iohub's Position.compute_pyramid)
+ *   bh_stitch_blend, bh_stitch_tile_lists
+ *                          <- biahub/stitch.py:196-311 write_output_chunk (one chunk per mosaic)
  *   bh_valid_mask, bh_bits_and, bh_bits_unpack
  *                          <- biahub/estimate_crop.py:58-94 estimate_crop_one_position (masks, counts, their AND)
  *   bh_blosc_unfilter, bh_blosc_filter
@@ -81,6 +83,7 @@ extern "C" {
 #define BH_DT_U16 1
 #define BH_DT_F32 2
 #define BH_DT_I16 3
+#define BH_DT_F16 4 /* IEEE binary16; accepted only as out_dtype of bh_stitch_blend */
 
 /* overhang fill modes (biahub/deskew.py:538-540) */
 #define BH_FILL_NONE 0
@@ -166,6 +169,32 @@ int bh_bin_finish(bh_ctx* ctx, const float* v, int64_t n, int apply, float sub, 
  * non-positive extent or a null pointer, before any device call.  Stream-ordered, no allocation, does not synchronise. */
 int bh_pyramid_downsample(bh_ctx* ctx, const void* in, int dtype, int64_t Z, int64_t Y, int64_t X, int method, int n,
                           void* const* out);
+
+/* ---- stitch: blend a well's FOVs into one mosaic (biahub/stitch.py:196-311 write_output_chunk) ------ */
+/* n_fov FOVs of one shape (Z, Y, X) and dtype in_dtype (BH_DT_U8, _U16, _I16, _F32) sit at integer offsets >= 0 in a mosaic:
+ * FOV voxel m lands at mosaic voxel m + offset.  out (device, C-contiguous (RZ, RY, RX), BH_DT_F32 or BH_DT_F16) receives the
+ * box of the mosaic that starts at region_origin and has region_extent:
+ *     out[o] = sum_i x_i[o] * w_i[o] / (sum_i w_i[o] + 1e-8)   over the FOVs covering o, in list order,
+ * w = d ** blending_exponent for d = min(y, Y-1-y, x, X-1-x) > 0 in the FOV's frame and 0 on its border (d = 0); voxels no FOV
+ * covers, or only border pixels cover, are exactly 0.  The weights are computed on the host (float64 pow) and rounded to
+ * float32; per voxel acc = fma(x_i, w_i, acc) and sw += w_i run in float32 in list order, then one correctly rounded division;
+ * float16 output is that float32 value rounded to nearest even, +-inf on overflow.  The bits of a voxel do not depend on the
+ * region.  fov: HOST array of n_fov device pointers, only read; offset_zyx: HOST, n_fov x 3.
+ * BH_ERR_INVALID before any device call for n_fov < 1, a null pointer, a non-positive extent, a negative offset or region
+ * origin, an unknown dtype, and a blending_exponent that is negative, NaN or overflows float32 at d = (min(Y, X) - 1) / 2.
+ * Stream-ordered; tile lists, pointer, offset and weight tables are staged into the context workspace with one copy from
+ * pageable memory; no stream or device synchronisation is issued. */
+int bh_stitch_blend(bh_ctx* ctx, int n_fov, const void* const* fov, const int64_t* offset_zyx, int in_dtype, int64_t Z, int64_t Y,
+                    int64_t X, double blending_exponent, const int64_t region_origin[3], const int64_t region_extent[3],
+                    int out_dtype, void* out);
+/* Host-only: the launch tiling bh_stitch_blend builds for this geometry.  tiling = {tile_y, tile_x, apron_x, nty, ntx}: tile
+ * (ty, tx) is rows [ty * tile_y, (ty + 1) * tile_y) and columns [tx * tile_x - apron_x, (tx + 1) * tile_x) of the region, clipped
+ * to it.  tile_off (nty * ntx + 1, may be NULL) and tile_fov (capacity entries, may be NULL) receive the CSR lists of the FOVs
+ * whose (y, x) footprint meets each tile, in FOV order; FOVs whose z range misses the region are in none.  n_entries = length of
+ * tile_fov. */
+int bh_stitch_tile_lists(int n_fov, const int64_t* offset_zyx, int64_t Z, int64_t Y, int64_t X, const int64_t region_origin[3],
+                         const int64_t region_extent[3], int64_t tiling[5], int32_t* tile_off, int32_t* tile_fov, int64_t capacity,
+                         int64_t* n_entries);
 
 /* ---- validity masks (crop estimation, biahub/estimate_crop.py:58-94) -------------------- */
 /* bits: ceil(n / 64) * 2 words on the device; voxel i -> bit i % 32 of word i / 32, set when the voxel is neither 0 nor
