@@ -17,6 +17,11 @@ permutations (shuffle / bit shuffle) are native code in libbhcore: HIP kernels (
 ``bh_blosc_filter``) so that a volume headed for the GPU is un-shuffled there, at HBM speed, instead of on a host core,
 and the same loops as host code (``bh_host_blosc_*``) for volumes that stay on the host.  Their NumPy restatement is
 oracle/codec_np.py (tests only).
+
+A compressed Blosc frame is parsed in one place: ``blosc_stream_table`` walks the block table, holds every rule about a
+malformed frame and bounds everything by the frame's own ``cbytes``.  The host decoder (``blosc_decode_blocks``) loops over
+that table; the device entry (``blosc_decode_frames_device``) uploads any mixture of lz4 and zstd frames in one pinned block
+and hands the same tables to ``bh_lz4_decompress_streams`` / ``bh_zstd_decompress_streams``, one launch per codec.
 """
 
 from __future__ import annotations
@@ -213,44 +218,67 @@ def _inner_decompress(codec: str, buf, nbytes: int) -> np.ndarray:
     raise NotImplementedError(f"blosc inner codec {codec!r} is not supported")
 
 
+def blosc_stream_table(buf, codec: str | None = None) -> tuple[BloscHeader, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The one walk over a compressed Blosc-1 frame's block table: ``(header, soff, csize, doff, dlen)`` — stream i is
+    ``csize[i]`` bytes at ``buf[soff[i]:]`` and decodes to ``dlen[i]`` still-permuted bytes at offset ``doff[i]`` of the chunk
+    (a block is one stream, or ``typesize`` streams when its writer split it; a stream with ``csize == dlen`` is stored raw).
+    ``codec`` ("lz4", "zstd", ...) demands that inner codec.  Every rule about a malformed frame lives here, and every bound is
+    ``header.cbytes``, never ``len(buf)``: the table fits the frame, every block starts behind it, every stream is non-empty and
+    ends inside the frame, a split block divides evenly — ValueError("corrupt blosc stream") otherwise.  Host-side parsing only."""
+    h = BloscHeader(buf)
+    if h.memcpyed or (codec is not None and h.codec != codec):
+        raise ValueError(f"not a compressed Blosc frame{'' if codec is None else f' with the {codec} inner codec'}")
+    corrupt = ValueError("corrupt blosc stream")
+    mv = memoryview(buf)
+    soff, csize, doff, dlen = [], [], [], []
+    if h.nbytes:
+        if h.blocksize == 0 or h.typesize == 0:
+            raise corrupt
+        nblocks = -(-h.nbytes // h.blocksize)
+        body = 16 + 4 * nblocks
+        if body > h.cbytes:
+            raise corrupt
+        bstarts = struct.unpack_from(f"<{nblocks}i", mv, 16)
+        may_split = (not h.flags & 0x10 and h.typesize <= _BLOSC_MAX_SPLITS
+                     and h.blocksize // h.typesize >= _BLOSC_MIN_BUFFERSIZE)
+        for b, pos in enumerate(bstarts):
+            o0 = b * h.blocksize
+            bsize = min(h.blocksize, h.nbytes - o0)
+            nsplits = h.typesize if may_split and bsize == h.blocksize else 1  # a short last block is never split
+            ne = bsize // nsplits
+            if pos < body or bsize % nsplits:  # (splits that would not tile their block)
+                raise corrupt
+            for j in range(nsplits):
+                if pos + 4 > h.cbytes:
+                    raise corrupt
+                (cb,) = struct.unpack_from("<i", mv, pos)
+                pos += 4
+                if cb <= 0 or pos + cb > h.cbytes:
+                    raise corrupt
+                soff.append(pos)
+                csize.append(cb)
+                doff.append(o0 + j * ne)
+                dlen.append(ne)
+                pos += cb
+    return h, np.asarray(soff, np.uint64), np.asarray(csize, np.uint32), np.asarray(doff, np.uint64), np.asarray(dlen, np.uint32)
+
+
 def blosc_decode_blocks(buf, out: np.ndarray | None = None) -> tuple[BloscHeader, np.ndarray]:
     """Entropy-decode a Blosc-1 stream WITHOUT undoing its shuffle: returns the header and the ``nbytes`` still-permuted
     bytes (block after block).  ``unfilter`` below — or ``bh_blosc_unfilter`` on the GPU — finishes the job."""
     h = BloscHeader(buf)
     mv = memoryview(buf)
+    # (the walk comes first: a header that lies about nbytes is refused before anything of that size is allocated)
+    streams = () if h.nbytes == 0 or h.memcpyed else blosc_stream_table(buf)[1:]
     if out is None:
         out = np.empty(h.nbytes, np.uint8)
     elif out.size != h.nbytes or out.dtype != np.uint8:
         raise ValueError("output buffer does not match the stream")
-    if h.nbytes == 0:
-        return h, out
-    if h.memcpyed:
+    if h.memcpyed and h.nbytes:
         out[:] = np.frombuffer(mv, np.uint8, h.nbytes, 16)
-        return h, out
-    nblocks = -(-h.nbytes // h.blocksize)
-    bstarts = struct.unpack_from(f"<{nblocks}i", mv, 16)
-    dont_split = bool(h.flags & 0x10)
     codec = h.codec
-    for b in range(nblocks):
-        o0 = b * h.blocksize
-        bsize = min(h.blocksize, h.nbytes - o0)
-        leftover = bsize != h.blocksize
-        split = (not dont_split and h.typesize <= _BLOSC_MAX_SPLITS
-                 and h.blocksize // h.typesize >= _BLOSC_MIN_BUFFERSIZE and not leftover)
-        nsplits = h.typesize if split else 1
-        ne = bsize // nsplits
-        pos = bstarts[b]
-        for j in range(nsplits):
-            (cb,) = struct.unpack_from("<i", mv, pos)
-            pos += 4
-            if cb < 0 or pos + cb > len(mv):
-                raise ValueError("corrupt blosc stream")
-            dst = out[o0 + j * ne: o0 + (j + 1) * ne]
-            if cb == ne:
-                dst[:] = np.frombuffer(mv, np.uint8, ne, pos)
-            else:
-                dst[:] = _inner_decompress(codec, mv[pos:pos + cb], ne)
-            pos += cb
+    for so, cb, do, ne in zip(*(a.tolist() for a in streams)):
+        out[do:do + ne] = np.frombuffer(mv, np.uint8, ne, so) if cb == ne else _inner_decompress(codec, mv[so:so + cb], ne)
     return h, out
 
 
@@ -418,141 +446,7 @@ def blosc_lz4_compress_device(filtered, nframes: int, cbytes: int, blocksize: in
     return packed, [int(v) for v in foff.cpu().tolist()]
 
 
-def blosc_lz4_stream_table(buf) -> tuple["BloscHeader", np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
-    """The LZ4 streams of a Blosc-1 frame with the lz4 inner codec: ``(header, soff, csize, doff, dlen)`` — stream i is
-    ``csize[i]`` bytes at ``buf[soff[i]:]`` and decodes to ``dlen[i]`` still-permuted bytes at offset ``doff[i]`` of the chunk
-    (a block is one stream, or ``typesize`` streams when its writer split it).  Host-side parsing only."""
-    h = BloscHeader(buf)
-    if h.codec != "lz4" or h.memcpyed:
-        raise ValueError("not a compressed Blosc frame with the lz4 inner codec")
-    mv = memoryview(buf)
-    nblocks = -(-h.nbytes // h.blocksize)
-    bstarts = struct.unpack_from(f"<{nblocks}i", mv, 16)
-    dont_split = bool(h.flags & 0x10)
-    soff, csize, doff, dlen = [], [], [], []
-    for b in range(nblocks):
-        o0 = b * h.blocksize
-        bsize = min(h.blocksize, h.nbytes - o0)
-        split = (not dont_split and h.typesize <= _BLOSC_MAX_SPLITS and h.blocksize // h.typesize >= _BLOSC_MIN_BUFFERSIZE
-                 and bsize == h.blocksize)
-        nsplits = h.typesize if split else 1
-        ne = bsize // nsplits
-        pos = bstarts[b]
-        for j in range(nsplits):
-            (cb,) = struct.unpack_from("<i", mv, pos)
-            pos += 4
-            if cb < 0 or pos + cb > len(mv):
-                raise ValueError("corrupt blosc stream")
-            soff.append(pos)
-            csize.append(cb)
-            doff.append(o0 + j * ne)
-            dlen.append(ne)
-            pos += cb
-    return h, np.asarray(soff, np.uint64), np.asarray(csize, np.uint32), np.asarray(doff, np.uint64), np.asarray(dlen, np.uint32)
-
-
-def blosc_lz4_decode_blocks_device(frame, out_dev, device=None) -> "BloscHeader":
-    """The device half of reading a Blosc-lz4 frame: ``frame`` (bytes-like, the whole frame as read from the store) is uploaded
-    COMPRESSED and its LZ4 streams are decoded by ``bh_lz4_decompress_streams`` into ``out_dev`` (uint8 device tensor of
-    ``header.nbytes`` still-permuted bytes; ``unfilter_device`` finishes).  Raises on a corrupt stream."""
-    import torch
-
-    from . import _lib
-    from .device import get_context, ptr
-
-    h, soff, csize, doff, dlen = blosc_lz4_stream_table(frame)
-    if out_dev.dtype != torch.uint8 or not out_dev.is_cuda or out_dev.numel() != h.nbytes or not out_dev.is_contiguous():
-        raise ValueError("output must be a contiguous uint8 device tensor of header.nbytes bytes")
-    dev = out_dev.device
-    fr = torch.frombuffer(bytearray(memoryview(frame)[: h.cbytes]), dtype=torch.uint8).to(dev)
-    tabs = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32)).to(dev) for a in (soff, csize, doff, dlen)]
-    ctx = get_context(dev)
-    with torch.cuda.device(dev):
-        _lib.check(ctx.lib.bh_lz4_decompress_streams(ctx.handle, ptr(fr), ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), ptr(tabs[3]),
-                                                     int(len(csize)), ptr(out_dev)))
-    return h
-
-
-def blosc_lz4_decode_frames_device(frames, out_dev, out_offsets) -> list["BloscHeader"]:
-    """Several Blosc-lz4 frames in ONE upload and ONE launch of ``bh_lz4_decompress_streams``: frame ``k`` decodes to
-    ``out_dev[out_offsets[k]: out_offsets[k] + header.nbytes]`` (uint8 device tensor, still-permuted bytes).  A volume's chunks
-    decoded one by one keep a few hundred wavefronts busy each and synchronise per chunk; together they fill the device."""
-    import torch
-
-    from . import _lib
-    from .device import get_context, ptr
-
-    if out_dev.dtype != torch.uint8 or not out_dev.is_cuda or not out_dev.is_contiguous():
-        raise ValueError("output must be a contiguous uint8 device tensor")
-    heads, tabs, pos = [], [[], [], [], []], 0
-    sizes = []
-    for fr, o in zip(frames, out_offsets):
-        h, soff, csize, doff, dlen = blosc_lz4_stream_table(fr)
-        if o < 0 or o + h.nbytes > out_dev.numel():
-            raise ValueError("frame does not fit the output tensor")
-        heads.append(h)
-        tabs[0].append(soff + np.uint64(pos))
-        tabs[1].append(csize)
-        tabs[2].append(doff + np.uint64(o))
-        tabs[3].append(dlen)
-        sizes.append(h.cbytes)
-        pos += (h.cbytes + 15) & ~15
-    if not heads:
-        return heads
-    host = torch.empty(pos, dtype=torch.uint8, pin_memory=True)
-    hv, q = host.numpy(), 0
-    for fr, nb in zip(frames, sizes):
-        hv[q:q + nb] = np.frombuffer(memoryview(fr)[:nb], np.uint8)
-        q += (nb + 15) & ~15
-    dev = out_dev.device
-    src = host.to(dev, non_blocking=True)
-    cat = [np.concatenate(t) for t in tabs]
-    dtabs = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a.view(np.int32)).to(dev) for a in cat]
-    ctx = get_context(dev)
-    with torch.cuda.device(dev):
-        _lib.check(ctx.lib.bh_lz4_decompress_streams(ctx.handle, ptr(src), ptr(dtabs[0]), ptr(dtabs[1]), ptr(dtabs[2]), ptr(dtabs[3]),
-                                                     int(len(cat[1])), ptr(out_dev)))
-    return heads
-
-
-def blosc_zstd_stream_table(buf) -> tuple["BloscHeader", np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
-    """The zstd streams of a Blosc-1 frame with the zstd inner codec: ``(header, soff, csize, doff, dlen)`` as
-    ``blosc_lz4_stream_table`` returns them (each stream one zstd frame, or a split c-blosc stored raw when ``csize ==
-    dlen``).  Every block start must lie behind the block table and every stream inside ``header.cbytes``; ValueError
-    ("corrupt blosc stream") otherwise.  Host-side parsing only."""
-    h = BloscHeader(buf)
-    if h.codec != "zstd" or h.memcpyed:
-        raise ValueError("not a compressed Blosc frame with the zstd inner codec")
-    mv = memoryview(buf)
-    nblocks = -(-h.nbytes // h.blocksize)
-    if h.cbytes > len(mv) or 16 + 4 * nblocks > h.cbytes:
-        raise ValueError("corrupt blosc stream")
-    bstarts = struct.unpack_from(f"<{nblocks}i", mv, 16)
-    dont_split = bool(h.flags & 0x10)
-    soff, csize, doff, dlen = [], [], [], []
-    for b in range(nblocks):
-        o0 = b * h.blocksize
-        bsize = min(h.blocksize, h.nbytes - o0)
-        split = (not dont_split and h.typesize <= _BLOSC_MAX_SPLITS and h.blocksize // h.typesize >= _BLOSC_MIN_BUFFERSIZE
-                 and bsize == h.blocksize)
-        nsplits = h.typesize if split else 1
-        ne = bsize // nsplits
-        pos = bstarts[b]
-        if pos < 16 + 4 * nblocks:
-            raise ValueError("corrupt blosc stream")
-        for j in range(nsplits):
-            if pos + 4 > h.cbytes:
-                raise ValueError("corrupt blosc stream")
-            (cb,) = struct.unpack_from("<i", mv, pos)
-            pos += 4
-            if cb <= 0 or pos + cb > h.cbytes:
-                raise ValueError("corrupt blosc stream")
-            soff.append(pos)
-            csize.append(cb)
-            doff.append(o0 + j * ne)
-            dlen.append(ne)
-            pos += cb
-    return h, np.asarray(soff, np.uint64), np.asarray(csize, np.uint32), np.asarray(doff, np.uint64), np.asarray(dlen, np.uint32)
+_DEVICE_DECODERS = {"lz4": "bh_lz4_decompress_streams", "zstd": "bh_zstd_decompress_streams"}  # csrc/lz4.hip, csrc/zstd.hip
 
 
 def _device_streams(fn_name: str, src, tabs, out_dev) -> None:
@@ -570,49 +464,46 @@ def _device_streams(fn_name: str, src, tabs, out_dev) -> None:
                                              int(len(tabs[1])), ptr(out_dev)))
 
 
-def blosc_zstd_decode_blocks_device(frame, out_dev) -> "BloscHeader":
-    """The device half of reading a Blosc-zstd frame: ``frame`` is uploaded COMPRESSED and its zstd streams are decoded by
-    ``bh_zstd_decompress_streams`` into ``out_dev`` (uint8 device tensor of ``header.nbytes`` still-permuted bytes;
-    ``unfilter_device`` finishes).  Raises on a corrupt stream."""
-    import torch
-
-    h, soff, csize, doff, dlen = blosc_zstd_stream_table(frame)
-    if out_dev.dtype != torch.uint8 or not out_dev.is_cuda or out_dev.numel() != h.nbytes or not out_dev.is_contiguous():
-        raise ValueError("output must be a contiguous uint8 device tensor of header.nbytes bytes")
-    fr = torch.frombuffer(bytearray(memoryview(frame)[: h.cbytes]), dtype=torch.uint8).to(out_dev.device)
-    _device_streams("bh_zstd_decompress_streams", fr, (soff, csize, doff, dlen), out_dev)
-    return h
-
-
-def blosc_zstd_decode_frames_device(frames, out_dev, out_offsets) -> list["BloscHeader"]:
-    """Several Blosc-zstd frames in ONE pinned upload and ONE launch of ``bh_zstd_decompress_streams``: frame ``k`` decodes to
-    ``out_dev[out_offsets[k]: out_offsets[k] + header.nbytes]`` (uint8 device tensor, still-permuted bytes)."""
+def blosc_decode_frames_device(frames, out_dev, out_offsets) -> list[BloscHeader]:
+    """The device half of reading Blosc frames whose inner codec is lz4 or zstd, in any mixture: the frames (bytes-like, as read
+    from the store) go up COMPRESSED in ONE pinned upload and their streams are decoded by ONE launch per inner codec present,
+    frame ``k`` to ``out_dev[out_offsets[k]: out_offsets[k] + header.nbytes]`` (uint8 device tensor, still-permuted bytes;
+    ``unfilter_device`` finishes).  Every table is built and validated on the host before anything touches the device.  A
+    volume's chunks decoded one by one keep a few hundred wavefronts busy each and synchronise per chunk; together they fill
+    the device.  Returns the headers in input order; raises on a corrupt stream."""
     import torch
 
     if out_dev.dtype != torch.uint8 or not out_dev.is_cuda or not out_dev.is_contiguous():
         raise ValueError("output must be a contiguous uint8 device tensor")
-    heads, tabs, sizes, pos = [], [[], [], [], []], [], 0
+    heads, tabs, pos = [], {}, 0
     for fr, o in zip(frames, out_offsets):
-        h, soff, csize, doff, dlen = blosc_zstd_stream_table(fr)
+        h, soff, csize, doff, dlen = blosc_stream_table(fr)
+        if h.codec not in _DEVICE_DECODERS:
+            raise ValueError(f"no device decoder for the blosc inner codec {h.codec!r}")
         if o < 0 or o + h.nbytes > out_dev.numel():
             raise ValueError("frame does not fit the output tensor")
         heads.append(h)
-        tabs[0].append(soff + np.uint64(pos))
-        tabs[1].append(csize)
-        tabs[2].append(doff + np.uint64(o))
-        tabs[3].append(dlen)
-        sizes.append(h.cbytes)
+        for col, a in zip(tabs.setdefault(h.codec, ([], [], [], [])), (soff + np.uint64(pos), csize, doff + np.uint64(o), dlen)):
+            col.append(a)
         pos += (h.cbytes + 15) & ~15
     if not heads:
         return heads
     host = torch.empty(pos, dtype=torch.uint8, pin_memory=True)
     hv, q = host.numpy(), 0
-    for fr, nb in zip(frames, sizes):
-        hv[q:q + nb] = np.frombuffer(memoryview(fr)[:nb], np.uint8)
-        q += (nb + 15) & ~15
+    for fr, h in zip(frames, heads):
+        hv[q:q + h.cbytes] = np.frombuffer(memoryview(fr)[: h.cbytes], np.uint8)
+        q += (h.cbytes + 15) & ~15
     src = host.to(out_dev.device, non_blocking=True)
-    _device_streams("bh_zstd_decompress_streams", src, [np.concatenate(t) for t in tabs], out_dev)
+    for name, cols in tabs.items():
+        _device_streams(_DEVICE_DECODERS[name], src, [np.concatenate(c) for c in cols], out_dev)
     return heads
+
+
+def blosc_decode_blocks_device(frame, out_dev) -> BloscHeader:
+    """One frame through ``blosc_decode_frames_device``, into an ``out_dev`` of exactly ``header.nbytes`` bytes."""
+    if out_dev.numel() != BloscHeader(frame).nbytes:
+        raise ValueError("output must be a contiguous uint8 device tensor of header.nbytes bytes")
+    return blosc_decode_frames_device([frame], out_dev, [0])[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------

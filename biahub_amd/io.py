@@ -532,11 +532,9 @@ class ZarrArray:
         plane = Y * X * self.dtype.itemsize
         tmp = None
         # LZ4 / zstd blocks -> permuted bytes on the device (csrc/lz4.hip, csrc/zstd.hip), in the slots the host decoder would
-        # have filled: every chunk of one codec in one upload and one launch
-        for name, decode in (("lz4", codecs.blosc_lz4_decode_frames_device), ("zstd", codecs.blosc_zstd_decode_frames_device)):
-            ks = [k for k in sorted(frames) if heads[k].codec == name]
-            if ks:
-                decode([frames[k] for k in ks], dstage, [k * cbytes for k in ks])
+        # have filled: every chunk in one upload, every chunk of one codec in one launch
+        ks = sorted(frames)
+        codecs.blosc_decode_frames_device([frames[k] for k in ks], dstage, [k * cbytes for k in ks])
         for i, (zi, kz, z0, iz) in enumerate(plan):
             h = heads[i]
             dst = out8[z0 * plane:min(Z, z0 + iz) * plane]
@@ -619,9 +617,28 @@ class ZarrArray:
                 full[: src.numel()] = src
                 src = full
             codecs.filter_device(src, dstage[i * cbytes:(i + 1) * cbytes], bsz, ts, mode)
-        per_file: dict = {}
         if prof:
             _mark("permutation")
+
+        def committer(blob_of):
+            """The host half, for the I/O threads: chunk i's frame, ``blob_of(i)``, goes to its own file or into its shard."""
+            per_file: dict = {}
+
+            def put(i):
+                zi, kz, z0, _ = plan[i]
+                blob = blob_of(i)
+                if kz is None:
+                    self._write_file(self._chunk_path((t, c, zi, 0, 0)), blob)
+                else:
+                    per_file.setdefault(zi, {})[(0, 0, kz, 0, 0)] = blob
+
+            def commit():
+                _io_map(put, range(len(plan)))
+                for zi, pieces in per_file.items():
+                    self._write_shard(self._chunk_path((t, c, zi, 0, 0)), pieces)
+
+            return commit
+
         if cfg.get("cname", "zstd") == "lz4" and cbytes >= 128 and os.environ.get("BH_LZ4_DEVICE", "1") != "0":
             # the block codec runs on the GPU too (csrc/lz4.hip): only the finished frames cross PCIe, the I/O threads just write
             packed, offs = codecs.blosc_lz4_compress_device(dstage, len(plan), cbytes, bsz, ts, mode)
@@ -631,39 +648,15 @@ class ZarrArray:
             if prof:
                 _mark("download")
 
-            def put(i):
-                zi, kz, z0, _ = plan[i]
+            def frame(i):
                 nb = int(np.frombuffer(hostp[offs[i] + 12: offs[i] + 16], np.uint32)[0])  # the frame's own length (header)
-                blob = hostp[offs[i]: offs[i] + nb]  # (a view of the pinned block: a bytes copy of it would hold the GIL for ~0.1 s per frame,
-                # stalling the operator's thread, which runs Python between its GPU calls)
-                if kz is None:
-                    self._write_file(self._chunk_path((t, c, zi, 0, 0)), blob)
-                else:
-                    per_file.setdefault(zi, {})[(0, 0, kz, 0, 0)] = blob
+                return hostp[offs[i]: offs[i] + nb]  # (a view of the pinned block: a bytes copy of it would hold the GIL for ~0.1 s per
+                # frame, stalling the operator's thread, which runs Python between its GPU calls)
 
-            def commit_frames():
-                _io_map(put, range(len(plan)))
-                for zi, pieces in per_file.items():
-                    self._write_shard(self._chunk_path((t, c, zi, 0, 0)), pieces)
-
-            return commit_frames
+            return committer(frame)
         host = to_host(dstage)
-
-        def one(i):
-            zi, kz, z0, _ = plan[i]
-            blob = codecs.blosc_compress(host[i * cbytes:(i + 1) * cbytes], ts, cfg.get("cname", "zstd"), cfg.get("clevel", 1),
-                                         mode, bsz, prefiltered=True)
-            if kz is None:
-                self._write_file(self._chunk_path((t, c, zi, 0, 0)), blob)
-            else:
-                per_file.setdefault(zi, {})[(0, 0, kz, 0, 0)] = blob
-
-        def commit():
-            _io_map(one, range(len(plan)))
-            for zi, pieces in per_file.items():
-                self._write_shard(self._chunk_path((t, c, zi, 0, 0)), pieces)
-
-        return commit
+        return committer(lambda i: codecs.blosc_compress(host[i * cbytes:(i + 1) * cbytes], ts, cfg.get("cname", "zstd"),
+                                                         cfg.get("clevel", 1), mode, bsz, prefiltered=True))
 
     def __getitem__(self, key) -> np.ndarray:
         if not isinstance(key, tuple):

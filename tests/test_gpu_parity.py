@@ -1653,7 +1653,7 @@ def test_lz4_device_decodes_c_blosc_streams(gpu):
             continue
         _, want = codecs.blosc_decode_blocks(stream)
         out = torch.empty(h.nbytes, dtype=torch.uint8, device=gpu)
-        codecs.blosc_lz4_decode_blocks_device(stream, out)
+        codecs.blosc_decode_blocks_device(stream, out)
         assert np.array_equal(out.cpu().numpy(), want), n
         raw = torch.empty_like(out)
         codecs.unfilter_device(out, raw, h.blocksize, h.typesize, h.shuffle_mode)
@@ -1662,12 +1662,12 @@ def test_lz4_device_decodes_c_blosc_streams(gpu):
     assert done >= 12
     # a damaged stream is reported, not decoded into garbage: the runs volume is a handful of long matches — zero their offsets
     bad = bytearray(z["lz4runs_u2_s2__blosc"].tobytes())
-    h, soff, csize, _, dlen = codecs.blosc_lz4_stream_table(bytes(bad))
+    h, soff, csize, _, dlen = codecs.blosc_stream_table(bytes(bad), codec="lz4")
     i = int(np.argmax(csize != dlen))  # the first compressed stream
     for k in range(int(soff[i]), int(soff[i]) + int(csize[i])):
         bad[k] = 0x0F if bad[k] else 0  # every token now announces a match after no literals, every offset reads 0 or 0x0f0f
     with pytest.raises(Exception, match="corrupt"):
-        codecs.blosc_lz4_decode_blocks_device(bytes(bad), torch.empty(h.nbytes, dtype=torch.uint8, device=gpu))
+        codecs.blosc_decode_blocks_device(bytes(bad), torch.empty(h.nbytes, dtype=torch.uint8, device=gpu))
 
 
 @pytest.mark.gpu
@@ -1711,7 +1711,7 @@ def test_lz4_device_compressor_frames(gpu, dtype, mode):
         stream = frame[: h.cbytes].tobytes()
         assert np.array_equal(codecs.blosc_decompress(stream), c.view(np.uint8)), i      # host decoder (pyarrow's lz4)
         out = torch.empty(cbytes, dtype=torch.uint8, device=gpu)
-        codecs.blosc_lz4_decode_blocks_device(stream, out)                                  # device decoder
+        codecs.blosc_decode_blocks_device(stream, out)                                  # device decoder
         assert torch.equal(out, filt[i * cbytes:(i + 1) * cbytes]), i
         if lib is not None:                                                                 # the real library
             buf = np.frombuffer(stream, np.uint8).copy()
@@ -1722,10 +1722,10 @@ def test_lz4_device_compressor_frames(gpu, dtype, mode):
     # every frame of the "volume" in one upload and one launch (what read_volume_device does)
     allout = torch.zeros_like(filt)
     fr = [host[offs[i]: offs[i + 1]].tobytes() for i in range(len(chunks))]
-    hs = codecs.blosc_lz4_decode_frames_device(fr, allout, [i * cbytes for i in range(len(chunks))])
+    hs = codecs.blosc_decode_frames_device(fr, allout, [i * cbytes for i in range(len(chunks))])
     assert len(hs) == len(chunks) and torch.equal(allout, filt)
     with pytest.raises(ValueError, match="fit"):
-        codecs.blosc_lz4_decode_frames_device(fr[:1], allout[: cbytes - 1], [0])
+        codecs.blosc_decode_frames_device(fr[:1], allout[: cbytes - 1], [0])
     # (a sine + Poisson noise wrapped into single bytes leaves LZ4 little to match: only the wider types must shrink there)
     assert sizes[0] < (0.8 if ts > 1 else 1.0) * cbytes and sizes[2] < 0.02 * cbytes and sizes[3] < 0.3 * cbytes, sizes
     nb = -(-cbytes // bsz)
@@ -2546,7 +2546,7 @@ def test_lz4_full_size_round_trip(gpu):
         host = packed[: offs[-1]].cpu().numpy()
         frames = [host[offs[i]: offs[i + 1]].tobytes() for i in range(nch)]
         back = torch.empty_like(stage)
-        heads = codecs.blosc_lz4_decode_frames_device(frames, back, [i * cbytes for i in range(nch)])
+        heads = codecs.blosc_decode_frames_device(frames, back, [i * cbytes for i in range(nch)])
         assert len(heads) == nch and torch.equal(back, stage)
         out = torch.empty_like(raw)
         for i in range(nch):

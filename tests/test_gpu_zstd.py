@@ -1,5 +1,6 @@
 """csrc/zstd.hip: Blosc-zstd chunks decoded on the GPU — c-blosc goldens, pyarrow's zstd across levels and data kinds, hand-built
 frames, corrupt input, the store route and a full-size volume."""
+import struct
 from pathlib import Path
 
 import numpy as np
@@ -40,7 +41,7 @@ def test_zstd_device_decodes_c_blosc_goldens(gpu):
             continue
         _, want = codecs.blosc_decode_blocks(stream)
         out = torch.empty(h.nbytes, dtype=torch.uint8, device=gpu)
-        codecs.blosc_zstd_decode_blocks_device(stream, out)
+        codecs.blosc_decode_blocks_device(stream, out)
         assert np.array_equal(out.cpu().numpy(), want), k
         raw = torch.empty_like(out)
         codecs.unfilter_device(out, raw, h.blocksize, h.typesize, h.shuffle_mode)
@@ -63,7 +64,7 @@ def test_zstd_device_decodes_pyarrow_corpus_in_one_launch(gpu):
                 want.append(codecs.blosc_decode_blocks(fr)[1])
     offs = np.cumsum([0] + [w.size for w in want[:-1]]).tolist()
     out = torch.zeros(sum(w.size for w in want), dtype=torch.uint8, device=gpu)
-    heads = codecs.blosc_zstd_decode_frames_device(frames, out, offs)
+    heads = codecs.blosc_decode_frames_device(frames, out, offs)
     assert len(heads) == len(frames) >= 80
     o = out.cpu().numpy()
     for k, (a, w) in enumerate(zip(offs, want)):
@@ -154,10 +155,10 @@ def test_zstd_device_full_size_volume(gpu):
         frames.append(codecs.blosc_compress(chunk.view(np.uint8).reshape(-1), 2, "zstd", 1, codecs.BLOSC_BITSHUFFLE, 32768))
         offs.append(z0 * Y * X * 2)
     h = codecs.BloscHeader(frames[0])
-    nstreams = sum(len(codecs.blosc_zstd_stream_table(f)[2]) for f in frames)
+    nstreams = sum(len(codecs.blosc_stream_table(f, codec="zstd")[2]) for f in frames)
     assert nstreams >= 16000
     out = torch.empty(Z * Y * X * 2, dtype=torch.uint8, device=gpu)
-    codecs.blosc_zstd_decode_frames_device(frames, out, offs)
+    codecs.blosc_decode_frames_device(frames, out, offs)
     vol = torch.empty_like(out)
     cb = h.nbytes
     for k in range(len(frames)):
@@ -166,3 +167,63 @@ def test_zstd_device_full_size_volume(gpu):
     for z0 in range(0, Z, cz):
         want = np.roll(plane, z0, axis=1)[None].repeat(cz, 0) + np.arange(cz, dtype=np.uint16)[:, None, None]
         assert np.array_equal(got[z0:z0 + cz], want), z0
+
+
+def _split_mode(frame):
+    """``frame`` rewritten as c-blosc's always-split mode writes it: every full block as ``typesize`` zstd streams."""
+    h, perm = codecs.blosc_decode_blocks(frame)
+    nb = -(-h.nbytes // h.blocksize)
+    body, starts = bytearray(), []
+    for b in range(nb):
+        blk = perm[b * h.blocksize:(b + 1) * h.blocksize]
+        starts.append(16 + 4 * nb + len(body))
+        for part in np.split(blk, h.typesize if blk.size == h.blocksize else 1):
+            s = codecs.zstd_compress(part, 1)
+            body += struct.pack("<i", len(s)) + s
+    head = struct.pack("<BBBBIII", frame[0], frame[1], frame[2] & ~0x10, h.typesize, h.nbytes, h.blocksize, 16 + 4 * nb + len(body))
+    return head + struct.pack(f"<{nb}i", *starts) + bytes(body)
+
+
+@pytest.mark.gpu
+def test_device_entry_mixed_codecs_in_one_batch(gpu):
+    """lz4 and zstd frames interleaved in one call of blosc_decode_frames_device: multi-block frames with a short last block
+    and frames with split blocks, into slots in reverse order with gaps between them; a malformed frame or a frame without a
+    device decoder anywhere in the batch is refused on the host, before the device is touched."""
+    z = np.load(GOLDEN / "blosc_streams.npz")
+    goldens = [z[k].tobytes() for k in sorted(z.files) if k.endswith("__blosc")]
+    heads = [codecs.BloscHeader(g) for g in goldens]
+
+    def first(codec, split):
+        return next(g for g, h in zip(goldens, heads) if h.codec == codec and not h.memcpyed and h.nbytes and bool(h.flags & 0x10) != split)
+
+    data = (np.arange((2 * 4096 + 1000) // 2) // 7 % 300).astype(np.uint16)
+    made = [codecs.blosc_compress(data, 2, c, 1, codecs.BLOSC_BITSHUFFLE, 4096) for c in ("lz4", "zstd")]
+    # no zstd golden is written in split mode (c-blosc splits only its fast codecs): the first one, rewritten that way
+    frames = [made[0], made[1], first("lz4", True), _split_mode(first("zstd", False))]
+    tabs = [codecs.blosc_stream_table(f) for f in frames]
+    assert [t[0].codec for t in tabs] == ["lz4", "zstd", "lz4", "zstd"]
+    assert [len(t[1]) for t in tabs[:2]] == [3, 3] and all(int(t[4][-1]) == 1000 for t in tabs[:2])
+    assert all(not t[0].flags & 0x10 and len(t[1]) > -(-t[0].nbytes // t[0].blocksize) for t in tabs[2:])
+    want = [codecs.blosc_decode_blocks(f)[1] for f in frames]
+    gap, offs, end = 48, [0] * len(frames), 48
+    for k in reversed(range(len(frames))):
+        offs[k] = end
+        end += want[k].size + gap
+    out = torch.full((end,), 0xA5, dtype=torch.uint8, device=gpu)
+    got = codecs.blosc_decode_frames_device(frames, out, offs)
+    assert [(h.codec, h.nbytes, h.cbytes) for h in got] == [(t[0].codec, t[0].nbytes, t[0].cbytes) for t in tabs]
+    o = out.cpu().numpy()
+    used = np.zeros(end, bool)
+    for k, (a, w) in enumerate(zip(offs, want)):
+        assert np.array_equal(o[a:a + w.size], w), k
+        used[a:a + w.size] = True
+    assert (~used).sum() == gap * (len(frames) + 1) and (o[~used] == 0xA5).all()
+    # refused on the host: nothing is allocated, uploaded or launched, so the output keeps its fill
+    out.fill_(0xA5)
+    bad = bytearray(frames[1])
+    struct.pack_into("<i", bad, 16, 8)
+    zlib_frame = codecs.blosc_compress(data, 2, "zlib", 1, codecs.BLOSC_BITSHUFFLE, 4096)
+    for batch in ([frames[0], bytes(bad)] + frames[2:], frames[:3] + [zlib_frame]):
+        with pytest.raises(ValueError):
+            codecs.blosc_decode_frames_device(batch, out, offs)
+        assert bool((out == 0xA5).all())

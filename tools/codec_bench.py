@@ -92,7 +92,7 @@ back = torch.empty_like(src)
 
 def decode_all():
     for i, fr in enumerate(frames):
-        codecs.blosc_lz4_decode_blocks_device(fr, back[i * cbytes:(i + 1) * cbytes])
+        codecs.blosc_decode_blocks_device(fr, back[i * cbytes:(i + 1) * cbytes])
 
 
 t, _ = timed(decode_all, reps=3)
@@ -100,7 +100,7 @@ assert torch.equal(back, filt)
 out["kernel_lz4_decompress_frames_incl_upload"] = {"ms": round(t * 1e3, 2), "GBps_out": round(src.numel() / t / 1e9, 1),
                                                    "note": "chunk by chunk: one upload, launch and synchronisation per frame"}
 back.zero_()
-t, _ = timed(lambda: codecs.blosc_lz4_decode_frames_device(frames, back, [i * cbytes for i in range(nchunks)]), reps=3)
+t, _ = timed(lambda: codecs.blosc_decode_frames_device(frames, back, [i * cbytes for i in range(nchunks)]), reps=3)
 assert torch.equal(back, filt)
 out["kernel_lz4_decompress_volume_incl_upload"] = {"ms": round(t * 1e3, 2), "GBps_out": round(src.numel() / t / 1e9, 1),
                                                    "note": "the volume's frames in one upload and one launch (read_volume_device)"}

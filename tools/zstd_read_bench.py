@@ -39,7 +39,7 @@ with tempfile.TemporaryDirectory(dir=tmpdir) as tmp:
     f = next(q for q in (p / "0").rglob("*") if q.is_file() and q.name != ".zarray" and not q.name.startswith("."))
     h = codecs.BloscHeader(f.read_bytes())
     out["stored_blocksize"] = h.blocksize
-    out["frames"] = sum(len(codecs.blosc_zstd_stream_table(q.read_bytes())[2]) for q in (p / "0").rglob("*")
+    out["frames"] = sum(len(codecs.blosc_stream_table(q.read_bytes(), codec="zstd")[2]) for q in (p / "0").rglob("*")
                         if q.is_file() and not q.name.startswith("."))
     modes = ("1",) if args.device_only else ("0", "1")
     times = {m: [] for m in modes}
