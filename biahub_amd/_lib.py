@@ -90,6 +90,7 @@ SIGNATURES = {
     "bh_richardson_lucy_destroy": (_int, [_vp]),
     "bh_richardson_lucy_info": (_int, [_vp, C.POINTER(_i64), C.POINTER(_int), C.POINTER(_int), C.POINTER(C.c_uint64)]),
     "bh_richardson_lucy_zpass": (_int, [_vp, C.POINTER(_int), C.POINTER(_int)]),
+    "bh_richardson_lucy_ztaps_real": (_int, [_vp, C.POINTER(_int)]),
     "bh_alloc_layout": (_int, [C.POINTER(_int), C.POINTER(_int), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bh_alloc_retained": (_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bh_torch_alloc": (_vp, [C.c_size_t, _int, _vp]),

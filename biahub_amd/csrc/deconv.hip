@@ -456,11 +456,12 @@ static bool use_fused_engine_any_order(int64_t Z, int64_t Y, int64_t X) {
 // order-sensitive 64-bit content hash of a small device array (one block; the PSF is a few thousand floats).  With `kept`
 // (the device copy of the PSF whose OTF is cached) out[1] also says whether the two arrays are equal word for word: a hash
 // match alone never validates the cache.  out[2]: the array equals its point mirror bit for bit (flat index i <-> n - 1 - i).
-__global__ __launch_bounds__(256) void content_hash_kernel(const uint32_t* __restrict__ data, int64_t n,
+// out[3]: every slice of `m` words (a z-slice of the PSF) equals its own point mirror bit for bit (r <-> m - 1 - r within it).
+__global__ __launch_bounds__(256) void content_hash_kernel(const uint32_t* __restrict__ data, int64_t n, int64_t m,
                                                            const uint32_t* __restrict__ kept, unsigned long long* out) {
     __shared__ unsigned long long sh[256];
-    __shared__ int differs, asym;
-    if (threadIdx.x == 0) differs = asym = 0;
+    __shared__ int differs, asym, slice_asym;
+    if (threadIdx.x == 0) differs = asym = slice_asym = 0;
     __syncthreads();
     unsigned long long h = 0xcbf29ce484222325ull ^ (unsigned long long)threadIdx.x;
     int diff = 0;
@@ -468,6 +469,8 @@ __global__ __launch_bounds__(256) void content_hash_kernel(const uint32_t* __res
         const uint32_t v = data[i];
         if (kept && kept[i] != v) diff = 1;
         if (data[n - 1 - i] != v) asym = 1;  // point symmetry h(-n) == h(n) of an array with odd extents: flat index i <-> n - 1 - i
+        const int64_t r = i % m;
+        if (data[i - r + (m - 1 - r)] != v) slice_asym = 1;  // (z, y, x) <-> (z, K1 - 1 - y, K2 - 1 - x)
         h ^= (unsigned long long)v + 0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1);
         h *= 0x100000001b3ull;
         h ^= h >> 29;
@@ -481,6 +484,7 @@ __global__ __launch_bounds__(256) void content_hash_kernel(const uint32_t* __res
         out[0] = t;
         out[1] = (kept && !differs) ? 1ull : 0ull;
         out[2] = asym ? 0ull : 1ull;
+        out[3] = slice_asym ? 0ull : 1ull;
     }
 }
 
@@ -505,7 +509,7 @@ static int stage_rl_psf(bh_ctx* ctx, const float* psf, int64_t pz, int64_t py, i
 // when `otf_real`; with zr >= 0 the compact z taps of that radius instead): spectrum scratch (auditioned once per allocation),
 // optional event timing, no host synchronisation otherwise.  Per iteration two 5-pass convolutions; the divide and the
 // multiply / clip ride in the inverse X passes.
-static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, int iterations, float eps,
+static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, bool zreal, int iterations, float eps,
                          float* out) {
     const size_t NS = fftconv_spectrum_elems(*pl);
     cf* spec;
@@ -520,10 +524,10 @@ static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
         BH_TRY(tune_rc);
     }
     ScopedIterTimer iter_timer(ctx, T_RL_ITER, iterations);
-    return fftconv_richardson_lucy(ctx, *pl, d, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, iterations, eps, out);
+    return fftconv_richardson_lucy(ctx, *pl, d, reinterpret_cast<const cf*>(otf), otf_real, zr, zreal, spec, iterations, eps, out);
 }
 
-// One read of the PSF on the device (one small kernel, a 24-byte read-back and a stream synchronisation) answers two things.
+// One read of the PSF on the device (one small kernel, a 32-byte read-back and a stream synchronisation) answers three things.
 // `same`: it equals `kept`, the device copy of the PSF a kept transfer function was built from, word for word.  (A pointer
 // match would not do instead: the adapters upload the PSF anew for every call, and a buffer that kept its address may have
 // changed its contents.)
@@ -531,18 +535,27 @@ static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
 // the bench's Gaussian) sits symmetric about the origin after staging, so its transfer function is REAL: the imaginary parts
 // the transforms leave are round-off.  The Z passes then read one float per bin instead of two (17.4 -> 8.7 GB per iteration
 // at config 2) and convolution and correlation are the same pass.  BH_RL_COMPLEX_OTF=1 keeps the general path (A/B switch).
-static int rl_probe_psf(bh_ctx* ctx, const float* psf, const int64_t K[3], const uint32_t* kept, bool* same, bool* real_form) {
+// `q_real`: odd y and x extents and every z-slice equal to its own 180-degree rotation in (y, x) bit for bit (every theoretical
+// PSF again, also one that is asymmetric along z): each slice sits symmetric about the origin of its plane after staging, so
+// Q(t; ky, kx), the PSF transformed along x and y only, is REAL by the same reasoning, and the compact z taps of the direct Z
+// pass are real.  Independent of `real_form`: a sheared point-symmetric PSF has a real transfer function and complex taps, a
+// z-asymmetric stack of symmetric slices the reverse.  BH_RL_COMPLEX_OTF=1 or BH_RL_ZREAL=0 (read here, i.e. when a handle is
+// created) keep the complex taps (A/B switches).
+static int rl_probe_psf(bh_ctx* ctx, const float* psf, const int64_t K[3], const uint32_t* kept, bool* same, bool* real_form,
+                        bool* q_real) {
     double* psum;
     BH_TRY(get_scratch(ctx, "rl_psum", 64, (void**)&psum));
     unsigned long long* dhash = reinterpret_cast<unsigned long long*>(psum) + 1;
-    unsigned long long hv[3] = {0, 0, 0};
+    unsigned long long hv[4] = {0, 0, 0, 0};
     hipStream_t s = ctx->stream;
     hipLaunchKernelGGL(content_hash_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(psf), K[0] * K[1] * K[2],
-                       kept, dhash);
+                       K[1] * K[2], kept, dhash);
     BH_CHECK_HIP(hipMemcpyAsync(hv, dhash, sizeof(hv), hipMemcpyDeviceToHost, s));
     BH_CHECK_HIP(hipStreamSynchronize(s));
     *same = kept != nullptr && hv[1] == 1ull;
     *real_form = (K[0] & 1) && (K[1] & 1) && (K[2] & 1) && hv[2] == 1ull && getenv("BH_RL_COMPLEX_OTF") == nullptr;
+    const char* zreal_env = getenv("BH_RL_ZREAL");
+    *q_real = (K[1] & 1) && (K[2] & 1) && hv[3] == 1ull && getenv("BH_RL_COMPLEX_OTF") == nullptr && !(zreal_env && atoi(zreal_env) == 0);
     return BH_OK;
 }
 
@@ -597,7 +610,7 @@ static bool engine_pad_box(const int64_t N[3], const int64_t K[3], int64_t P[3])
 // asks for — by the kernel that also multiplies, clips and rebuilds the wrap-extension for the next iteration.
 // rl_padded_run: the iterations with the transfer function of the box in hand (NS complex, or NS floats when `otf_real`); no
 // host synchronisation unless the context is timing.
-static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, const int64_t N[3],
+static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* otf, bool otf_real, int zr, bool zreal, const int64_t N[3],
                          const int64_t K[3], const int64_t P[3], int iterations, float eps, float* out) {
     const int64_t VP = P[0] * P[1] * P[2];
     hipStream_t s = ctx->stream;
@@ -639,11 +652,11 @@ static int rl_padded_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
     ScopedIterTimer iter_timer(ctx, T_RL_ITER, iterations);
     float *cur = a, *nxt = b;
     if (wrap) {  // the last pass stores the result cropped: no crop kernel
-        BH_TRY(fftconv_richardson_lucy_wrap(ctx, *pl, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, spec_b, a, b, N, K,
+        BH_TRY(fftconv_richardson_lucy_wrap(ctx, *pl, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, zreal, spec, spec_b, a, b, N, K,
                                             iterations, eps, out));
     } else {
         for (int it = 0; it < iterations; ++it) {
-            BH_TRY(fftconv_rl_iteration_padded(ctx, *pl, cur, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, spec, eps, c));
+            BH_TRY(fftconv_rl_iteration_padded(ctx, *pl, cur, dp, reinterpret_cast<const cf*>(otf), otf_real, zr, zreal, spec, eps, c));
             hipLaunchKernelGGL(fold_update_rewrap_kernel, grid2(fold.P), dim3(256), 0, s, (const float*)c, (const float*)cur, nxt, fold);
             std::swap(cur, nxt);
         }
@@ -1013,6 +1026,7 @@ struct bh_rl {
     size_t otf_bytes = 0;
     bool otf_real = false;
     int zr = -1;               // >= 0: `otf` holds the compact z taps of this radius (fftconv_make_ztaps), the Z passes convolve directly
+    bool zreal = false;        // those taps are real (rl_probe_psf's q_real): imaginary halves zero, the real-tap kernels run
     float* psf = nullptr;      // library back-end: the PSF itself (rl_library_run builds its transfer function per call)
 };
 
@@ -1022,6 +1036,7 @@ struct RlCreateOpts {
                        // else in a block of the filter pool, the set-up's transients in scratch going back to the driver
     bool ztaps;        // fftconv_ztaps_radius may choose the direct Z pass (not with use_scratch: the taps have no scratch of their own)
     bool real_otf;     // keep the real form: the caller's rl_probe_psf said the PSF has one, and the entry takes it
+    bool q_real;       // rl_probe_psf said Q is real: z taps, if the handle keeps any, are real
 };
 
 // The set-up of every Richardson-Lucy entry at the box and back-end rl_plan picked: normalise, pad, centre and transform the
@@ -1054,6 +1069,7 @@ static int rl_create_impl(bh_ctx* ctx, const float* psf, const int64_t K[3], con
     h->otf_real = opts.real_otf;
     // the PSF's z-extent fits the compiled taps: R + 1 (real) or 2R + 1 planes of taps instead of the Z planes of the transfer function
     h->zr = opts.ztaps ? fftconv_ztaps_radius(*h->plan, K[0]) : -1;
+    h->zreal = h->zr >= 0 && opts.q_real;
     h->otf_bytes = h->zr >= 0 ? fftconv_ztaps_elems(*h->plan, h->zr, h->otf_real) * sizeof(cf) : NS * (h->otf_real ? sizeof(float) : sizeof(cf));
     // the complex transfer function is what is kept, or (only its real part or the z taps are) a transient in scratch "fc_otf"
     const bool transient = h->otf_real || h->zr >= 0;
@@ -1074,7 +1090,7 @@ static int rl_create_impl(bh_ctx* ctx, const float* psf, const int64_t K[3], con
     if ((rc = get_scratch(ctx, "rl_psum", 64, (void**)&psum)) != BH_OK) return fail(rc);
     if ((rc = stage_rl_psf(ctx, psf, K[0], K[1], K[2], box[0], box[1], box[2], real, psum)) != BH_OK) return fail(rc);
     if (h->zr >= 0) {
-        if ((rc = fftconv_make_ztaps(ctx, *h->plan, real, h->otf_real, h->zr, otf_c, reinterpret_cast<cf*>(h->otf))) != BH_OK) return fail(rc);
+        if ((rc = fftconv_make_ztaps(ctx, *h->plan, real, h->otf_real, h->zreal, h->zr, otf_c, reinterpret_cast<cf*>(h->otf))) != BH_OK) return fail(rc);
     } else if ((rc = fftconv_make_otf(ctx, *h->plan, real, otf_c)) != BH_OK) {
         return fail(rc);
     } else if (h->otf_real) {
@@ -1097,11 +1113,11 @@ static int rl_apply_impl(bh_ctx* ctx, const bh_rl* h, const float* d, int iterat
     if (h->backend == BH_RL_ENGINE) {
         // the last update pass can leave the row sums of its result behind (what a deskew with a mean fill wants of this volume)
         if (row_sums) fftconv_arm_rowsums(*h->plan, row_sums);
-        const int st = rl_engine_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, iterations, eps, out);
+        const int st = rl_engine_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, h->zreal, iterations, eps, out);
         if (row_sums) *produced = fftconv_rowsums_taken(*h->plan) && st == BH_OK ? 1 : 0;
         return st;
     }
-    return rl_padded_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, h->N, h->K, h->box, iterations, eps, out);
+    return rl_padded_run(ctx, h->plan, d, h->otf, h->otf_real, h->zr, h->zreal, h->N, h->K, h->box, iterations, eps, out);
 }
 
 // What both public entries do before anything else: keep the data term aside when the estimate overwrites it (in == out), and
@@ -1132,9 +1148,9 @@ int bh_richardson_lucy_create(bh_ctx* ctx, const float* psf, int64_t pz, int64_t
     const int64_t K[3] = {pz, py, px}, N[3] = {Z, Y, X};
     int64_t box[3];
     const int backend = rl_plan(pz, py, px, Z, Y, X, box);
-    RlCreateOpts opts = {false, true, false};
+    RlCreateOpts opts = {false, true, false, false};
     bool same;
-    if (backend != BH_RL_LIBRARY) BH_TRY(rl_probe_psf(ctx, psf, K, nullptr, &same, &opts.real_otf));
+    if (backend != BH_RL_LIBRARY) BH_TRY(rl_probe_psf(ctx, psf, K, nullptr, &same, &opts.real_otf, &opts.q_real));
     return rl_create_impl(ctx, psf, K, N, box, backend, opts, out);
 }
 
@@ -1176,6 +1192,12 @@ int bh_richardson_lucy_info(const bh_rl* h, int64_t box[3], int* backend, int* o
     return BH_OK;
 }
 
+int bh_richardson_lucy_ztaps_real(const bh_rl* h, int* real) {
+    BH_REQUIRE(h != nullptr, "NULL argument");
+    if (real) *real = h->zreal ? 1 : 0;
+    return BH_OK;
+}
+
 int bh_richardson_lucy_zpass(const bh_rl* h, int* direct, int* taps) {
     BH_REQUIRE(h != nullptr, "NULL argument");
     if (direct) *direct = h->zr >= 0 ? 1 : 0;
@@ -1203,8 +1225,8 @@ int bh_richardson_lucy(bh_ctx* ctx, const float* in, const float* psf, int64_t p
     if (done) return BH_OK;
     ScopedTimer timer(ctx, T_RL_TOTAL);
     bh_rl* h = ctx->rl_oneshot;
-    RlCreateOpts opts = {true, false, false};
-    bool hit = false;
+    RlCreateOpts opts = {true, false, false, false};  // no taps: q_real stays unused
+    bool hit = false, q_real;
     const size_t psf_bytes = (size_t)(pz * py * px) * sizeof(float);
     uint32_t* kept = nullptr;  // device copy of the PSF the kept handle was built from
     if (backend == BH_RL_ENGINE) {
@@ -1213,7 +1235,7 @@ int bh_richardson_lucy(bh_ctx* ctx, const float* in, const float* psf, int64_t p
         bool same_key = h != nullptr && h->plan == pl;
         for (int a = 0; a < 3; ++a) same_key = same_key && h->K[a] == K[a] && h->N[a] == N[a];
         BH_TRY(get_scratch(ctx, "rl_psf_kept", psf_bytes, (void**)&kept));
-        BH_TRY(rl_probe_psf(ctx, psf, K, same_key ? kept : nullptr, &hit, &opts.real_otf));
+        BH_TRY(rl_probe_psf(ctx, psf, K, same_key ? kept : nullptr, &hit, &opts.real_otf, &q_real));
         hit = hit && h->otf_real == opts.real_otf;
     }
     if (!hit) {  // (an engine set-up drops the kept handle before it rebuilds in the same scratch; a library one leaves it alone)

@@ -210,7 +210,10 @@ size_t fftconv_ztaps_elems(const ConvPlan& pl, int R, bool hermitian) {
 // taps from Q = the PSF transformed along x and y (z natural), scaled by 2 Z / V: the factor fftconv_make_otf puts in H (2 / V)
 // times the Z of the unnormalised inverse Z transform the direct pass no longer runs.  Hermitian: t = 0..R as
 // (Q(t) + conj(Q(-t))) / 2 — exactly the taps whose transform is Re(H), the real transfer function of the FFT path.
-__global__ void ztaps_extract_kernel(const cf* __restrict__ Q, cf* __restrict__ taps, long ncol, int Z, int R, int hermitian, float scale) {
+// zreal: Q is real (rl_probe_psf), the imaginary halves the transforms leave are round-off and are written as zero; the planes
+// keep their layout, the real-tap kernels of the direct pass read the real halves only.
+__global__ void ztaps_extract_kernel(const cf* __restrict__ Q, cf* __restrict__ taps, long ncol, int Z, int R, int hermitian, int zreal,
+                                     float scale) {
     const int nq = hermitian ? R + 1 : 2 * R + 1;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (long)nq * ncol; i += (long)gridDim.x * blockDim.x) {
         const int k = (int)(i / ncol);
@@ -223,19 +226,20 @@ __global__ void ztaps_extract_kernel(const cf* __restrict__ Q, cf* __restrict__ 
             const int t = k - R;
             v = cscale(Q[(long)((t + Z) % Z) * ncol + j], scale);
         }
+        if (zreal) v.y = 0.f;
         taps[i] = v;
     }
 }
 
 // `work`: a spectrum-sized scratch (fftconv_spectrum_elems), overwritten
-int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, int R, cf* work, cf* taps) {
+int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, bool zreal, int R, cf* work, cf* taps) {
     const double V = (double)pl.d.Z * pl.d.Y * pl.d.X;
     const long ncol = (long)pl.d.Y * pl.d.XP;
     BH_TRY(launch_x(ctx, pl, false, 0, padded_psf, work, nullptr, nullptr, 0.f));
     BH_TRY(launch_col(ctx, pl, COL_FWD, false, work, nullptr, 1.f));
     const long n = (long)(hermitian ? R + 1 : 2 * R + 1) * ncol;
     hipLaunchKernelGGL(ztaps_extract_kernel, dim3((unsigned)std::min<long>(ceil_div(n, 256), 65535)), dim3(256), 0, ctx->stream, work,
-                       taps, ncol, pl.d.Z, R, hermitian ? 1 : 0, (float)(2.0 * pl.d.Z / V));
+                       taps, ncol, pl.d.Z, R, hermitian ? 1 : 0, zreal ? 1 : 0, (float)(2.0 * pl.d.Z / V));
     BH_CHECK_HIP(hipGetLastError());
     return BH_OK;
 }
@@ -410,8 +414,9 @@ int fftconv_apply_staged_filter(bh_ctx* ctx, const ConvPlan& pl, const float* in
 //                            [Xinv -> est = max(est*.,0) (stored) -> Xfwd] }   (last iteration: no trailing Xfwd)
 // 8 passes and 84 B/voxel per iteration instead of 10 passes and 96 B/voxel.
 // `est` is output only: the first pass fills it with max(d, 0).
-// zr >= 0: `otf` holds the compact z taps of that radius (fftconv_make_ztaps) and the Z passes are direct convolutions.
-int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, cf* spec,
+// zr >= 0: `otf` holds the compact z taps of that radius (fftconv_make_ztaps) and the Z passes are direct convolutions;
+// zreal: those taps are real (their imaginary halves were written as zero) and the real-tap kernels run.
+int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, bool zreal, cf* spec,
                             int iterations, float eps, float* est) {
     if (iterations <= 0) return BH_OK;
     // otf_real: `otf` holds one float per bin (the transfer function of a point-symmetric PSF); convolution and correlation
@@ -419,11 +424,11 @@ int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, con
     BH_TRY(launch_x(ctx, pl, false, 0, d, spec, est, nullptr, 0.f));  // est = max(d, 0) written by the same pass
     for (int it = 0; it < iterations; ++it) {
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-        BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec, otf));
+        BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, zreal, spec, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
         BH_TRY(launch_x(ctx, pl, true, XE_RATIO, nullptr, spec, nullptr, d, eps, true));
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-        BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec, otf));
+        BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, zreal, spec, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
         BH_TRY(launch_x(ctx, pl, true, XE_UPDATE, nullptr, spec, est, est, eps, it + 1 < iterations));
     }
@@ -496,14 +501,14 @@ int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, float* est, size_t by
 // the caller folds its wrapped-around tails back, multiplies, and rebuilds est_p.  9 transform passes (8 when nothing is
 // padded and update -> forward can stay fused).
 int fftconv_rl_iteration_padded(bh_ctx* ctx, const ConvPlan& pl, const float* est_p, const float* d_p, const cf* otf,
-                                bool otf_real, int zr, cf* spec, float eps, float* corr_p) {
+                                bool otf_real, int zr, bool zreal, cf* spec, float eps, float* corr_p) {
     BH_TRY(launch_x(ctx, pl, false, 0, est_p, spec, nullptr, nullptr, 0.f));
     BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-    BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec, otf));
+    BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, zreal, spec, otf));
     BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
     BH_TRY(launch_x(ctx, pl, true, XE_RATIO, nullptr, spec, nullptr, d_p, eps, true));
     BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec, nullptr, 1.f));
-    BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec, otf));
+    BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, zreal, spec, otf));
     BH_TRY(launch_col(ctx, pl, COL_INV, false, spec, nullptr, 1.f));
     BH_TRY(launch_x(ctx, pl, true, XE_STORE, nullptr, spec, corr_p, nullptr, 0.f));
     return BH_OK;
@@ -527,7 +532,7 @@ bool fftconv_rl_wrap_supported(const ConvPlan& pl, const int64_t N[3], const int
 // d_p: the data on the box, wrap-extended like the estimate (lo below, hi above): the first pass clips it into est_a
 // (e0 = max(d, 0)) and transforms it in one go.  est_a / est_b alternate; the last update is stored straight into `out`, the
 // UNPADDED (N[0], N[1], N[2]) result volume.
-int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, cf* spec_a,
+int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, bool zreal, cf* spec_a,
                                  cf* spec_b, float* est_a, float* est_b, const int64_t N[3], const int64_t K[3], int iterations,
                                  float eps, float* out) {
     const int64_t P[3] = {pl.d.Z, pl.d.Y, pl.d.X};
@@ -542,11 +547,11 @@ int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d
     BH_TRY(launch_x(ctx, pl, false, 0, d_p, spec_a, cur, nullptr, 0.f));  // est = max(d, 0) written by the same pass
     for (int it = 0; it < iterations; ++it) {
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec_a, nullptr, 1.f));
-        BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, spec_a, otf));
+        BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, zreal, spec_a, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec_a, nullptr, 1.f));
         BH_TRY(launch_xw_wrap(ctx, pl, xw::FUSED_RATIO_WRAP, spec_a, spec_b, nullptr, d_p, eps, wr[0], wr[2]));
         BH_TRY(launch_col(ctx, pl, COL_FWD, false, spec_b, nullptr, 1.f));
-        BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, spec_b, otf));
+        BH_TRY(launch_rl_z(ctx, pl, true, otf_real, zr, zreal, spec_b, otf));
         BH_TRY(launch_col(ctx, pl, COL_INV, false, spec_b, nullptr, 1.f));
         if (it + 1 == iterations) {  // the last update is needed on the volume's own voxels only: stored cropped
             BH_TRY(launch_xw_wrap(ctx, pl, xw::INV_UPDATE_CROP, spec_b, nullptr, out, cur, eps, we[0], we[2]));

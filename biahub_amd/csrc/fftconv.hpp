@@ -61,7 +61,7 @@ bool fftconv_rowsums_taken(ConvPlan& pl);
 int fftconv_make_otf(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, cf* otf);
 int fftconv_ztaps_radius(const ConvPlan& pl, int64_t pz);
 size_t fftconv_ztaps_elems(const ConvPlan& pl, int R, bool hermitian);
-int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, int R, cf* work, cf* taps);
+int fftconv_make_ztaps(bh_ctx* ctx, const ConvPlan& pl, const float* padded_psf, bool hermitian, bool zreal, int R, cf* work, cf* taps);
 int fftconv_stage_inverse_filter(bh_ctx* ctx, const ConvPlan& pl, const void* tf, bool tf_complex, float reg, bool bf16,
                                  void* filt);
 
@@ -75,12 +75,12 @@ int fftconv_tikhonov(bh_ctx* ctx, const ConvPlan& pl, const float* in, const flo
                      float* filt, float* out);
 
 // ---- Richardson-Lucy ----
-int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, cf* spec,
+int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, const cf* otf, bool otf_real, int zr, bool zreal, cf* spec,
                             int iterations, float eps, float* est);
 int fftconv_rl_iteration_padded(bh_ctx* ctx, const ConvPlan& pl, const float* est_p, const float* d_p, const cf* otf,
-                                bool otf_real, int zr, cf* spec, float eps, float* corr_p);
+                                bool otf_real, int zr, bool zreal, cf* spec, float eps, float* corr_p);
 bool fftconv_rl_wrap_supported(const ConvPlan& pl, const int64_t N[3], const int64_t K[3], const int64_t P[3]);
-int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, cf* spec_a,
+int fftconv_richardson_lucy_wrap(bh_ctx* ctx, const ConvPlan& pl, const float* d_p, const cf* otf, bool otf_real, int zr, bool zreal, cf* spec_a,
                                  cf* spec_b, float* est_a, float* est_b, const int64_t N[3], const int64_t K[3], int iterations,
                                  float eps, float* out);
 

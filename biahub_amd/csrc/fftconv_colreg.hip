@@ -150,26 +150,27 @@ int fftconv_ztaps_radius(const ConvPlan& pl, int64_t pz) {
     if (env_off("BH_RL_ZDIRECT")) return -1;
     const int r = (int)(pz / 2);
     for (int rc : {4, zdirect::RMAX})
-        if (r <= rc) return (pl.d.Z > 2 * rc && pl.d.Z >= rc + zdirect::D) ? rc : -1;
+        if (r <= rc) return (pl.d.Z > 2 * rc && pl.d.Z >= rc + zdirect::D_RULE) ? rc : -1;
     return -1;
 }
 
-template <int R>
+template <int R, bool REALQ>
 static int launch_zdirect_r(bh_ctx* ctx, const zdirect::Params& p, int mode) {
     const long nwaves = ceil_div(p.ncol, 64);
     const dim3 grid((unsigned)ceil_div(nwaves, zdirect::NT / 64));
     switch (mode) {
-        case COL_FILTER: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_FILTER>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
-        case COL_CONV: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_CONV>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
-        default: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_CORR>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
+        case COL_FILTER: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_FILTER, REALQ>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
+        case COL_CONV: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_CONV, REALQ>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
+        default: hipLaunchKernelGGL((zdirect::zdirect_kernel<R, COL_CORR, REALQ>), grid, dim3(zdirect::NT), 0, ctx->stream, p); break;
     }
     BH_CHECK_HIP(hipGetLastError());
     return BH_OK;
 }
 
-// The Z pass of one R-L convolution (corr = false) or correlation (corr = true): with the taps of radius zr the direct pass,
-// with the full transfer function (zr < 0) the FFT Z pass launch_col picks
-int launch_rl_z(bh_ctx* ctx, const ConvPlan& pl, bool corr, bool otf_real, int zr, cf* S, const cf* otf) {
+// The Z pass of one R-L convolution (corr = false) or correlation (corr = true): with the taps of radius zr the direct pass
+// (zreal: the taps are real, the kernels that drop their imaginary halves), with the full transfer function (zr < 0) the FFT
+// Z pass launch_col picks
+int launch_rl_z(bh_ctx* ctx, const ConvPlan& pl, bool corr, bool otf_real, int zr, bool zreal, cf* S, const cf* otf) {
     const int mode = otf_real ? COL_FILTER : (corr ? COL_CORR : COL_CONV);
     if (zr < 0) return launch_col(ctx, pl, mode, true, S, otf, 1.f);
     zdirect::Params p;
@@ -177,10 +178,11 @@ int launch_rl_z(bh_ctx* ctx, const ConvPlan& pl, bool corr, bool otf_real, int z
     p.taps = otf;
     p.ncol = (long)pl.d.Y * pl.d.XP;
     p.Z = pl.d.Z;
-    BH_REQUIRE(p.Z > 2 * zr && p.Z >= zr + zdirect::D, "internal: %d z taps on columns of %d", 2 * zr + 1, p.Z);
+    BH_REQUIRE(p.Z > 2 * zr && p.Z >= zr + zdirect::D_RULE, "internal: %d z taps on columns of %d", 2 * zr + 1, p.Z);
     switch (zr) {
-        case 4: return launch_zdirect_r<4>(ctx, p, mode);
-        case zdirect::RMAX: return launch_zdirect_r<zdirect::RMAX>(ctx, p, mode);
+        case 4: return zreal ? launch_zdirect_r<4, true>(ctx, p, mode) : launch_zdirect_r<4, false>(ctx, p, mode);
+        case zdirect::RMAX:
+            return zreal ? launch_zdirect_r<zdirect::RMAX, true>(ctx, p, mode) : launch_zdirect_r<zdirect::RMAX, false>(ctx, p, mode);
         default: BH_REQUIRE(false, "internal: no direct Z pass of radius %d", zr);
     }
     return BH_OK;

@@ -553,7 +553,7 @@ int launch_col_pass(bh_ctx* ctx, ColParams p, int mode);
 // kernel for that column length
 int launch_col(bh_ctx* ctx, const ConvPlan& pl, int mode, bool zaxis, cf* S, const cf* otf, float scale, int pcc_norm = 0,
                int pcc_swap = 0, cf* otf_out = nullptr);
-int launch_rl_z(bh_ctx* ctx, const ConvPlan& pl, bool corr, bool otf_real, int zr, cf* S, const cf* otf);
+int launch_rl_z(bh_ctx* ctx, const ConvPlan& pl, bool corr, bool otf_real, int zr, bool zreal, cf* S, const cf* otf);
 bool colw_tables(int64_t n, std::vector<cf>& tab);
 bool colz_tables(const ConvDims& d, std::vector<cf>& tab);
 bool colz3_tables(const ConvDims& d, std::vector<cf>& tab);

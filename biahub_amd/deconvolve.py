@@ -179,6 +179,10 @@ class PreparedRichardsonLucy:
         # "direct": the Z passes convolve along z with `z_taps` compact taps; "fft": the Z FFT with the full transfer function
         self.z_pass = "direct" if direct.value else "fft"
         self.z_taps = int(taps.value)
+        taps_real = ctypes.c_int()
+        _lib.check(self._ctx.lib.bh_richardson_lucy_ztaps_real(self._handle, ctypes.byref(taps_real)))
+        # the taps of the direct pass are real (every z-slice of the PSF equals its own 180-degree rotation): the real-tap kernels
+        self.z_taps_real = bool(taps_real.value)
 
     def __call__(self, zyx, iterations: int = 10, eps: float = 1e-6, out: torch.Tensor | None = None,
                  row_sums: torch.Tensor | None = None):

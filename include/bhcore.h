@@ -383,6 +383,11 @@ int bh_richardson_lucy_info(const bh_rl* handle, int64_t box[3], int* backend, i
  * direct convolutions along z with `taps` = 2R + 1 taps and the handle keeps those taps instead of the transfer function),
  * 0 for the FFT Z pass (taps = 0; also the library back-end, and any handle created with BH_RL_ZDIRECT=0).  Either may be NULL. */
 int bh_richardson_lucy_zpass(const bh_rl* handle, int* direct, int* taps);
+/* real = 1 when the handle runs the direct Z pass with REAL taps: the PSF's y and x extents are odd and every z-slice equals
+ * its own 180-degree rotation in (y, x) bit for bit, so the PSF transformed along x and y only is real and the imaginary
+ * halves of the taps (round-off) are dropped.  0 otherwise, also for the FFT Z pass and for handles created with
+ * BH_RL_ZREAL=0 or BH_RL_COMPLEX_OTF=1.  `real` may be NULL. */
+int bh_richardson_lucy_ztaps_real(const bh_rl* handle, int* real);
 
 /* Phase cross-correlation of two equally shaped float32 volumes (biahub/estimate_stabilization.py:199-256
  * phase_cross_corr): corr = irfftn(F1 conj(F2) / norm), norm = 1 | max(|F1 conj F2|, eps) | |F1||F2|.
