@@ -7,7 +7,9 @@
 // samples of 64 neighbouring pixels in LDS (one coalesced read of the volume) and every lane finds its own column's order
 // statistic by a most-significant-bit-first search on order-preserving integer keys: 16 counting sweeps over LDS for
 // uint16 camera data, 32 for float32 — no sorting, no data-dependent branches, and the result is the exact element
-// np.median picks (for an even count the mean of the two middle elements, computed in the reference's type).
+// np.median picks (for an even count the mean of the two middle elements, computed in the reference's type).  float32 takes
+// one more sweep, which counts the NaN samples of a column: np.median of a column that holds a NaN is NaN, while the keys
+// order NaN above +inf or below -inf by its sign bit.
 // The apply pass re-reads the volume once: out = float32(double(v) / pattern * mean) for integer input (the reference's
 // float64 expression, cast by _flat_field_czyx :154), float32 arithmetic for float32 input.
 #include "common.hpp"
@@ -89,6 +91,13 @@ __global__ __launch_bounds__(FF_NT) void median_z_kernel(const TIN* __restrict__
             buf ^= 1;  // the other buffer is only rewritten after the next barrier
             return s;
         };
+        bool has_nan = false;
+        if constexpr (sizeof(TIN) == 4) {  // float32: a column holding any NaN has the median NaN, as np.median gives it
+            unsigned c = 0;      // NaN keys lie outside [key(-inf), key(+inf)] = [0x007fffff, 0xff800000]
+#pragma unroll 8
+            for (int j = 0; j < nz; ++j) c += (unsigned)(mine[j * zs] > 0xff800000u || mine[j * zs] < 0x007fffffu);
+            has_nan = total(c) != 0;
+        }
         for (int bit = K::bits - 1; bit >= 0; --bit) {
             const unsigned cand = res | (1u << bit);
             unsigned c = 0;
@@ -119,7 +128,7 @@ __global__ __launch_bounds__(FF_NT) void median_z_kernel(const TIN* __restrict__
                 m = (double)(((float)K::from(res) + (float)K::from(hi)) * 0.5f);  // np.median of float32 stays float32
             else
                 m = (K::from(res) + K::from(hi)) * 0.5;
-            pattern[(size_t)y * X + x0 + col] = (Z & 1) ? K::from(res) : m;
+            pattern[(size_t)y * X + x0 + col] = has_nan ? (double)NAN : ((Z & 1) ? K::from(res) : m);
         }
     }
 }

@@ -137,7 +137,7 @@ int bh_memcpy_d2h(bh_ctx* ctx, void* dst, const void* src, uint64_t bytes); /* s
 /* ---- flat field (the step before deskew in the mantis pipeline) -------------------------------------------- */
 /* pattern[y*X + x] (device, float64) = np.median(in[:, y, x]) exactly: the middle element, or for an even Z the mean of
  * the two middle elements (float32 mean for float32 input, like numpy).  BH_ERR_UNSUPPORTED when Z samples of 4 pixels
- * do not fit the LDS staging (Z > 18432 for 16-bit input, 9216 for float32).  NaN input is not supported. */
+ * do not fit the LDS staging (Z > 18432 for 16-bit input, 9216 for float32).  A float32 column that holds a NaN gives NaN, like numpy. */
 int bh_median_z(bh_ctx* ctx, const void* in, int in_dtype, int64_t Z, int64_t Y, int64_t X, double* pattern);
 
 /* out = in / pattern * mean(pattern), pattern = median along Z (biahub/flat_field.py:101-120), written as float32 like
