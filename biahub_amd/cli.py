@@ -869,32 +869,78 @@ def pyramid_cli(input_position_dirpaths, sbatch_filepath, local, levels, method)
 @click.option("--flipud", is_flag=True, help="Flip images up-down before stitching")
 @click.option("--flipxy", is_flag=True, help="Flip images along the diagonal before stitching")
 @click.option("--pcc-channel-name", default=None, type=str,
-              help="(phase cross-correlation refinement of the reference: not available here)")
-@click.option("--local", "-l", is_flag=True, default=False, help="Accepted for compatibility: this verb runs on the host.")
+              help="Channel to register neighbouring FOVs on by phase cross-correlation; the shifts are then solved for consistent "
+                   "positions that replace the stage's y and x (default: none, metadata only). FOV names must be XXXYYY grid cells.")
+@click.option("--pcc-z-index", default=0, type=int, show_default=True, help="Z slice index used for the phase cross-correlation")
+@click.option("--pcc-overlap", default=300, type=int, show_default=True,
+              help="Width in pixels of the strips of neighbouring FOVs that are registered (the reference fixes 300)")
+@click.option("--add_offset", is_flag=True,
+              help="Accepted as in the reference, which never reads it: it has no effect.")
+@click.option("--local", "-l", is_flag=True, default=False, help="Accepted for compatibility: this verb runs in-process.")
 @click.option("--monitor", "-m", is_flag=True, default=False, help="Accepted for compatibility.")
-def estimate_stitch_cli(input_position_dirpaths, output_filepath, fliplr, flipud, flipxy, pcc_channel_name, local, monitor):
+def estimate_stitch_cli(input_position_dirpaths, output_filepath, fliplr, flipud, flipxy, pcc_channel_name, pcc_z_index, pcc_overlap,
+                        add_offset, local, monitor):
     """Estimate stitching translations, in pixels, from the plate's micro-manager stage positions and the scale metadata
-    (reference: ``biahub estimate-stitch`` without ``--pcc-channel-name``, estimate_stitch.py:16-64, 118-213).  Host only."""
+    (reference: ``biahub estimate-stitch``, estimate_stitch.py:16-64, 118-213).  Host only, unless ``--pcc-channel-name`` asks for
+    the refinement: neighbouring FOVs are then registered on their overlap strips on the GPU (estimate_stitch.py:155-191)."""
     from .io import _read_group_attrs
     from .stitch import estimate_stitch_translations, extract_stage_position
 
-    if pcc_channel_name is not None:
-        raise click.UsageError("--pcc-channel-name (pairwise phase cross-correlation and the shift-graph optimiser) is not "
-                               "available in biahub_amd; use the reference biahub package for it.")
     plate_path = Path(input_position_dirpaths[0]).parents[2]
+    names = ["/".join(Path(p).parts[-3:]) for p in input_position_dirpaths]
+    refine = None
+    if pcc_channel_name is not None:
+        refine = _stitch_refinement(dict(zip(names, input_position_dirpaths)), pcc_channel_name, pcc_z_index, pcc_overlap, flipud, fliplr)
     plate_attrs = _read_group_attrs(plate_path)
     click.echo("Reading stage positions...")
     stage = {}
-    for p in input_position_dirpaths:
-        name = "/".join(Path(p).parts[-3:])
+    for name, p in zip(names, input_position_dirpaths):
         with open_ome_zarr(p) as pos:
             label = pos.zattrs["omero"]["name"]
         stage[name] = extract_stage_position(plate_attrs, label)
         click.echo(f"Found metadata: {name}: {stage[name]}")
     with open_ome_zarr(input_position_dirpaths[0]) as pos:
         scale_zyx = pos.scale[2:]
-    translations = estimate_stitch_translations(stage, scale_zyx, fliplr=fliplr, flipud=flipud, flipxy=flipxy)
+    translations = estimate_stitch_translations(stage, scale_zyx, fliplr=fliplr, flipud=flipud, flipxy=flipxy, refine=refine)
     model_to_yaml(StitchSettings(channels=None, total_translation=translations), output_filepath)
+
+
+def _stitch_refinement(paths_by_name: dict, channel_name: str, z_index: int, overlap: int, flipud: bool, fliplr: bool):
+    """Check everything ``--pcc-channel-name`` needs (click.UsageError otherwise; no GPU call, nothing written) and return the
+    ``refine`` hook of ``estimate_stitch_translations``."""
+    from . import estimate_stitch as es
+
+    wells: dict = {}
+    for name in paths_by_name:
+        wells.setdefault("/".join(name.split("/")[:2]), []).append(name)
+    try:
+        cells = {well: es.parse_grid_names(fovs) for well, fovs in wells.items()}
+    except ValueError as e:
+        raise click.UsageError(f"--pcc-channel-name reads each FOV's grid cell from its name XXXYYY, as the reference biahub package "
+                               f"does; {e}") from e
+    first = True
+    for well, fovs in wells.items():
+        relations = {r for _, _, r in es.hilbert_edges(cells[well])[1]}
+        for name in fovs:
+            with open_ome_zarr(paths_by_name[name]) as pos:
+                channels, shape = pos.channel_names, pos.data.shape
+            if first and channel_name not in channels:
+                raise click.UsageError(f"--pcc-channel-name {channel_name!r}: the input has {channels}")
+            first = False
+            if not 0 <= z_index < shape[2]:
+                raise click.UsageError(f"--pcc-z-index {z_index}: {name} has {shape[2]} z slices")
+            try:
+                es.check_overlap(overlap, shape[-2:], relations)
+            except ValueError as e:
+                raise click.UsageError(f"--pcc-overlap: {e} ({name})") from e
+    with open_ome_zarr(next(iter(paths_by_name.values()))) as pos:
+        channel_index = pos.channel_names.index(channel_name)
+
+    def refine(well, fov_names, pixel_zyx):
+        return es.refine_translations({n: paths_by_name[n] for n in fov_names}, pixel_zyx, channel_index, z_index, overlap,
+                                      flipud=flipud, fliplr=fliplr)
+
+    return refine
 
 
 @cli.command("stitch")

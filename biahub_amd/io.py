@@ -348,6 +348,48 @@ class ZarrArray:
         _io_map(one, self._spatial_blocks())
         return out
 
+    def read_plane(self, t: int, c: int, z: int) -> np.ndarray:
+        """The (Y, X) plane z of volume (t, c): only the chunks (of a shard: the inner chunks) that hold z are read and decoded."""
+        T, C, Z, Y, X = self.shape
+        if not (0 <= t < T and 0 <= c < C and 0 <= z < Z):
+            raise IndexError(f"(t, c, z) = ({t}, {c}, {z}) outside {self.shape[:3]}")
+        ct, cc, cz, cy, cx = self.chunks
+        it, ic, iz, iy, ix = self.inner
+        out = np.empty((Y, X), self.dtype)
+        zi, zr = divmod(z, cz)
+
+        def place(arr5, tt, cc_, zz, y0, x0):  # arr5: a decoded (inner) chunk whose plane zz is plane z, corner at (y0, x0)
+            y1, x1 = min(Y, y0 + arr5.shape[3]), min(X, x0 + arr5.shape[4])
+            out[y0:y1, x0:x1] = arr5[tt, cc_, zz, : y1 - y0, : x1 - x0]
+
+        def one(blk):
+            yi, xi = blk
+            y0, x0 = yi * cy, xi * cx
+            y1, x1 = min(Y, y0 + cy), min(X, x0 + cx)
+            try:
+                fh = open(self._chunk_path((t // ct, c // cc, zi, yi, xi)), "rb")
+            except FileNotFoundError:
+                out[y0:y1, x0:x1] = self.fill_value
+                return
+            with fh:
+                if not self.sharded:
+                    place(self._decode(fh.read()), t % ct, c % cc, zr, y0, x0)
+                    return
+                index = self._read_index(fh, os.fstat(fh.fileno()).st_size)
+                st, sc, kz = (t % ct) // it, (c % cc) // ic, zr // iz
+                for ky in range(-(-(y1 - y0) // iy)):
+                    for kx in range(-(-(x1 - x0) // ix)):
+                        off, nb = (int(v) for v in index[st, sc, kz, ky, kx])
+                        r0, s0 = y0 + ky * iy, x0 + kx * ix
+                        if off == _MISSING and nb == _MISSING:
+                            out[r0:min(Y, r0 + iy), s0:min(X, s0 + ix)] = self.fill_value
+                            continue
+                        fh.seek(off)
+                        place(self._decode(fh.read(nb)), (t % ct) % it, (c % cc) % ic, zr % iz, r0, s0)
+
+        _io_map(one, [(yi, xi) for yi in range(-(-Y // cy)) for xi in range(-(-X // cx))])
+        return out
+
     def write_volume(self, t: int, c: int, vol: np.ndarray) -> None:
         T, C, Z, Y, X = self.shape
         if vol.shape != (Z, Y, X):

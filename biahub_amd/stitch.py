@@ -236,17 +236,22 @@ def extract_stage_position(plate_zattrs: dict, position_name: str) -> tuple[floa
     return zpos, ypos, xpos
 
 
-def estimate_stitch_translations(stage_zyx: dict, scale_zyx, fliplr=False, flipud=False, flipxy=False) -> dict:
+def estimate_stitch_translations(stage_zyx: dict, scale_zyx, fliplr=False, flipud=False, flipxy=False, refine=None) -> dict:
     """{FOV name "row/col/fov": [z, y, x] in pixels} from stage positions in micrometres (biahub/estimate_stitch.py:135-206): per
-    well, zero-based, divided by the scale, flipped, shifted to non-negative, rounded to 2 decimals."""
+    well, zero-based, divided by the scale, flipped, shifted to non-negative, rounded to 2 decimals.  ``refine(well, names,
+    pixel_zyx)``, when given, is called per well before the flips and returns None or (i, j): positions that replace the y and x
+    columns (``estimate_stitch.refine_translations``)."""
     wells: dict = {}
     for key, value in stage_zyx.items():
         wells.setdefault("/".join(key.split("/")[:2]), {})[key] = value
     out = {}
-    for well in wells.values():
+    for well_name, well in wells.items():
         a = np.array(list(well.values()), np.float64)
         a -= a.min(axis=0)
         a /= np.asarray(scale_zyx, np.float64)
+        refined = refine(well_name, list(well), a) if refine is not None else None
+        if refined is not None:
+            a[:, 1], a[:, 2] = refined
         if fliplr:
             a[:, 2] *= -1
         if flipud:

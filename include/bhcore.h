@@ -14,6 +14,7 @@
  *   bh_pyramid_downsample  <- biahub/pyramid.py:19-40 pyramid (iohub's Position.compute_pyramid)
  *   bh_stitch_blend, bh_stitch_tile_lists
  *                          <- biahub/stitch.py:196-311 write_output_chunk (one chunk per mosaic)
+ *   bh_stitch_edge_shifts  <- biahub/vendor/stitch/tile.py:126-160 offset, _dexp_shim.py:139-182 register_translation_nd
  *   bh_valid_mask, bh_bits_and, bh_bits_unpack
  *                          <- biahub/estimate_crop.py:58-94 estimate_crop_one_position (masks, counts, their AND)
  *   bh_blosc_unfilter, bh_blosc_filter
@@ -195,6 +196,31 @@ int bh_stitch_blend(bh_ctx* ctx, int n_fov, const void* const* fov, const int64_
 int bh_stitch_tile_lists(int n_fov, const int64_t* offset_zyx, int64_t Z, int64_t Y, int64_t X, const int64_t region_origin[3],
                          const int64_t region_extent[3], int64_t tiling[5], int32_t* tile_off, int32_t* tile_fov, int64_t capacity,
                          int64_t* n_entries);
+
+/* Pairwise registration of neighbouring FOVs on their overlap strips (biahub/vendor/stitch/tile.py:126-160 offset,
+ * _dexp_shim.py:32-182 register_translation_nd).  Edge e pairs tile_a[e] with tile_b[e], both (Y, X) planes of
+ * `dtype` (uint8, uint16, int16, float32), only read; b lies below a (BH_STITCH_BELOW: the last `overlap` rows of a against the
+ * first `overlap` rows of b) or to its right (BH_STITCH_RIGHT: columns).  flipud / fliplr flip every tile (rows, then columns)
+ * before the strips are cut; the flips are folded into the strip addressing.  Per strip, in float64: minus its minimum when
+ * that is negative; Gaussian sigma 1.5 (radius 6, scipy "reflect", axis 0 then 1); log1p twice; |sobel 0| + |sobel 1|
+ * ("reflect"); times sqrt(hann) per axis.  corr = fftshift(Re ifft2(R / (|R| + 1e-6))), R = F(a) conj(F(b)).  Peak: noise floor
+ * = the 0.999 quantile of every 16th element of corr[:c0-r0, :c1-r1] (r = int(0.45 n), c = n / 2; the mean of that selection
+ * when the quantile is not finite), crop to [c-r, c+r), max(x, floor) - floor, Gaussian sigma 1.5 "wrap", first maximum in C
+ * order; confidence = (peak - max outside the peak's window) / (1e-6 + peak), the window [p-m, p+m) per axis taken as a numpy
+ * slice (a negative start counts from the end: the window is then usually empty and the confidence exactly 0).
+ * shift (HOST, n_edges x 2: y, x) = peak - r, plus (Y - overlap, 0) for BELOW and (0, X - overlap) for RIGHT; confidence (HOST,
+ * n_edges).  prepared (HOST array of 2 n_edges device pointers, or NULL): prepared[2e], prepared[2e+1] receive the prepared
+ * strips of a and b, float32 (overlap, X) or (Y, overlap); corr_shifted (HOST array of n_edges device pointers, or NULL):
+ * the shifted correlation, same shape (both rounded from the float64 the call works in).  Every edge's bits equal those of
+ * a one-edge call.
+ * BH_ERR_INVALID before any device call for n_edges < 1, a null pointer, an unknown dtype or relation, Y or X < 16, and
+ * overlap < 16 or beyond the tile's extent along the strip axis.  Work is enqueued for all edges of a relation at once; the
+ * stream is synchronised once, before the results are read. */
+#define BH_STITCH_BELOW 0
+#define BH_STITCH_RIGHT 1
+int bh_stitch_edge_shifts(bh_ctx* ctx, int n_edges, const void* const* tile_a, const void* const* tile_b, const int32_t* relation,
+                          int dtype, int64_t Y, int64_t X, int64_t overlap, int flipud, int fliplr, double* shift,
+                          double* confidence, float* const* prepared, float* const* corr_shifted);
 
 /* ---- validity masks (crop estimation, biahub/estimate_crop.py:58-94) -------------------- */
 /* bits: ceil(n / 64) * 2 words on the device; voxel i -> bit i % 32 of word i / 32, set when the voxel is neither 0 nor
