@@ -14,7 +14,7 @@ INCLUDE = PKG.parent / "include"
 LIB = PKG / "libbhcore.so"
 # longest compiles first (the pool below starts sources in this order): pyramid.hip alone takes longer than any other file, then
 # the kernel families of the FFT engine
-SOURCES = ["pyramid.hip", "fftconv_col.hip", "fftconv_xtile.hip", "fftconv_xw.hip", "fftconv_colreg.hip", "deskew.hip", "stitch.hip", "stitch_pcc.hip", "affine.hip", "fftconv.hip", "context.hip", "fill.hip", "deconv.hip", "spline.hip", "copy.hip", "regmetric.hip", "flatfield.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "zstd.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
+SOURCES = ["pyramid.hip", "fftconv_col.hip", "fftconv_xtile.hip", "fftconv_xw.hip", "fftconv_colreg.hip", "deskew.hip", "stitch.hip", "stitch_pcc.hip", "affine.hip", "fftconv.hip", "context.hip", "fill.hip", "deconv.hip", "spline.hip", "copy.hip", "regmetric.hip", "flatfield.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "zstd.hip", "zstd_enc.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
 ARCH = "gfx950"
 
 
@@ -30,7 +30,8 @@ _FC = ("fftconv.hpp", "fftconv_dev.hpp")
 INCLUDES = {"fftconv.hip": _FC, "fftconv_col.hip": _FC, "fftconv_xtile.hip": _FC + ("fftconv_xpass.inc",), "fftconv_xw.hip": _FC + ("fftconv_xw.inc", "fftconv_x3.inc"),
             "fftconv_colreg.hip": _FC + ("fftconv_xw.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"),
             "deconv.hip": ("fftconv.hpp",), "invtf.hip": ("fftconv.hpp",), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
-            "deskew.hip": ("deskew_geom.hpp", "deskew_rows.inc"), "host_deskew.hip": ("deskew_geom.hpp",), "zstd.hip": ("zstd_frame.inc", "zstd_block.inc")}
+            "deskew.hip": ("deskew_geom.hpp", "deskew_rows.inc"), "host_deskew.hip": ("deskew_geom.hpp",), "lz4.hip": ("blosc_frame.hpp",),
+            "zstd.hip": ("zstd_frame.inc", "zstd_block.inc", "zstd_tables.inc"), "zstd_enc.hip": ("zstd_enc.inc", "zstd_tables.inc", "blosc_frame.hpp")}
 
 
 def needs_build() -> bool:

@@ -31,7 +31,8 @@ def _output_compressor():
     zstd level 1 and bit shuffle (NGFF 0.4: numcodecs ``Blosc``; 0.5: the zarr v3 ``blosc`` codec).  BH_ZARR_COMPRESSOR =
     none | blosc | blosc-lz4 | zstd | zlib overrides it.  ``blosc-lz4`` keeps the container and the bit shuffle and swaps the
     inner codec for lz4 — any Blosc reader (numcodecs, iohub) takes it — which lets the GPU run the block codec too
-    (csrc/lz4.hip): a device-resident result then crosses PCIe compressed and the host only writes files."""
+    (csrc/lz4.hip): a device-resident result then crosses PCIe compressed and the host only writes files.  With the default
+    ``blosc`` and BH_ZSTD_ENCODE_DEVICE=1 the GPU writes the zstd frames themselves (csrc/zstd_enc.hip), to the same effect."""
     import os
 
     kind = os.environ.get("BH_ZARR_COMPRESSOR", "blosc").lower()

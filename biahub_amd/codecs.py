@@ -419,31 +419,59 @@ def filter_device(src, dst, blocksize: int, typesize: int, mode: int) -> None:
     _device_filter("bh_blosc_filter", src, dst, blocksize, typesize, mode)
 
 
+def _blosc_compress_device(cname: str, filtered, nframes: int, cbytes: int, blocksize: int, typesize: int, mode: int):
+    """The device block codecs' common entry (``bh_blosc_<cname>_bound`` / ``bh_blosc_<cname>_compress``, one contract)."""
+    import torch
+
+    from . import _lib
+    from .device import get_context, ptr
+
+    if cbytes < _BLOSC_MIN_BUFFERSIZE:
+        raise ValueError("chunks below 128 bytes are stored raw by Blosc: compress them on the host")
+    if not isinstance(filtered, torch.Tensor) or filtered.dtype != torch.uint8 or not filtered.is_cuda or not filtered.is_contiguous() \
+            or filtered.numel() != nframes * cbytes:
+        raise ValueError("need a contiguous uint8 device tensor of nframes * cbytes bytes")
+    ctx = get_context(filtered.device)
+    bound = int(getattr(ctx.lib, f"bh_blosc_{cname}_bound")(int(nframes), int(cbytes), int(blocksize)))
+    packed = torch.empty(bound, dtype=torch.uint8, device=filtered.device)
+    foff = torch.empty(nframes + 1, dtype=torch.int64, device=filtered.device)
+    with torch.cuda.device(filtered.device):
+        _lib.check(getattr(ctx.lib, f"bh_blosc_{cname}_compress")(ctx.handle, ptr(filtered), int(nframes), int(cbytes), int(blocksize),
+                                                                  int(typesize), int(mode), ptr(packed), ptr(foff)))
+    return packed, [int(v) for v in foff.cpu().tolist()]
+
+
 def blosc_lz4_compress_device(filtered, nframes: int, cbytes: int, blocksize: int, typesize: int, mode: int):
     """Blosc-1 frames (inner codec lz4) of ``nframes`` chunks of ``cbytes`` bytes each, ON the GPU (``bh_blosc_lz4_compress``).
     ``filtered``: uint8 device tensor of ``nframes * cbytes`` bytes already permuted block by block (``filter_device`` with this
     ``blocksize``).  Returns ``(packed, offsets)``: the frames in one uint8 device tensor and a host list of ``nframes + 1``
     offsets (frame f = ``packed[offsets[f]: ...]``, its own length in its header; the last entry is the total) — only the
     compressed bytes need to cross PCIe.  Synchronises once (the offsets are read back)."""
+    return _blosc_compress_device("lz4", filtered, nframes, cbytes, blocksize, typesize, mode)
+
+
+def blosc_zstd_compress_device(filtered, nframes: int, cbytes: int, blocksize: int, typesize: int, mode: int):
+    """``blosc_lz4_compress_device`` for the container's zstd inner codec — the format iohub stores use by default
+    (``bh_blosc_zstd_compress``, csrc/zstd_enc.hip): every block one zstd frame that any zstd decoder reads."""
+    return _blosc_compress_device("zstd", filtered, nframes, cbytes, blocksize, typesize, mode)
+
+
+def zstd_compress_host(buf) -> bytes:
+    """One zstd frame of ``buf`` from the library's OWN encoder on the CPU (``bh_host_zstd_compress``: the source of the device
+    encoder compiled with one lane), or ``buf`` itself when the frame would not be smaller — the Blosc container's mark for a
+    stored block.  ``zstd_compress`` (libzstd) is what the host writers use; this one exists to test and debug the encoder."""
     import ctypes
 
-    import torch
-
     from . import _lib
-    from .device import get_context, ptr
 
-    if filtered.dtype != torch.uint8 or not filtered.is_cuda or not filtered.is_contiguous() or filtered.numel() != nframes * cbytes:
-        raise ValueError("need a contiguous uint8 device tensor of nframes * cbytes bytes")
-    if cbytes < _BLOSC_MIN_BUFFERSIZE:
-        raise ValueError("chunks below 128 bytes are stored raw by Blosc: compress them on the host")
-    ctx = get_context(filtered.device)
-    bound = int(ctx.lib.bh_blosc_lz4_bound(int(nframes), int(cbytes), int(blocksize)))
-    packed = torch.empty(bound, dtype=torch.uint8, device=filtered.device)
-    foff = torch.empty(nframes + 1, dtype=torch.int64, device=filtered.device)
-    with torch.cuda.device(filtered.device):
-        _lib.check(ctx.lib.bh_blosc_lz4_compress(ctx.handle, ptr(filtered), int(nframes), int(cbytes), int(blocksize), int(typesize),
-                                                 int(mode), ptr(packed), ptr(foff)))
-    return packed, [int(v) for v in foff.cpu().tolist()]
+    raw = np.ascontiguousarray(np.frombuffer(memoryview(buf), np.uint8))
+    if raw.size == 0:
+        raise ValueError("nothing to compress")
+    dst = np.empty(raw.size, np.uint8)
+    csize = ctypes.c_uint64(0)
+    _lib.check(_lib.load().bh_host_zstd_compress(raw.ctypes.data_as(ctypes.c_void_p), raw.size, dst.ctypes.data_as(ctypes.c_void_p),
+                                                 dst.size, ctypes.byref(csize)))
+    return dst[: csize.value].tobytes()
 
 
 _DEVICE_DECODERS = {"lz4": "bh_lz4_decompress_streams", "zstd": "bh_zstd_decompress_streams"}  # csrc/lz4.hip, csrc/zstd.hip

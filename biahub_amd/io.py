@@ -597,7 +597,8 @@ class ZarrArray:
     def write_volume_device(self, t: int, c: int, vol) -> None:
         """Store a device tensor as the (t, c) volume.  For Blosc plane-stack chunks the shuffle runs on the GPU
         (``bh_blosc_filter``), with the lz4 inner codec the block codec too (``bh_blosc_lz4_compress``: only compressed frames
-        cross PCIe); the download lands in pinned memory and the I/O threads run the entropy coder (zstd / zlib) or just write."""
+        cross PCIe; with the zstd inner codec and ``BH_ZSTD_ENCODE_DEVICE=1``, ``bh_blosc_zstd_compress`` does the same); the
+        download lands in pinned memory and the I/O threads run the entropy coder (zstd / zlib) or just write."""
         self.encode_volume_device(t, c, vol)()
 
     def encode_volume_device(self, t: int, c: int, vol):
@@ -681,11 +682,16 @@ class ZarrArray:
 
             return commit
 
-        if cfg.get("cname", "zstd") == "lz4" and cbytes >= 128 and os.environ.get("BH_LZ4_DEVICE", "1") != "0":
-            # the block codec runs on the GPU too (csrc/lz4.hip): only the finished frames cross PCIe, the I/O threads just write
-            packed, offs = codecs.blosc_lz4_compress_device(dstage, len(plan), cbytes, bsz, ts, mode)
+        cname = cfg.get("cname", "zstd")
+        lz4_dev = cname == "lz4" and os.environ.get("BH_LZ4_DEVICE", "1") != "0"
+        zstd_dev = cname == "zstd" and os.environ.get("BH_ZSTD_ENCODE_DEVICE", "0") == "1"  # opt-in: the default route is the host's libzstd
+        if cbytes >= 128 and (lz4_dev or zstd_dev):
+            # the block codec runs on the GPU too (csrc/lz4.hip, csrc/zstd_enc.hip): only the finished frames cross PCIe, the I/O
+            # threads just write
+            compress = codecs.blosc_lz4_compress_device if lz4_dev else codecs.blosc_zstd_compress_device
+            packed, offs = compress(dstage, len(plan), cbytes, bsz, ts, mode)
             if prof:
-                _mark("lz4 + frames")
+                _mark(f"{cname} + frames")
             hostp = to_host(packed[: offs[-1]])
             if prof:
                 _mark("download")

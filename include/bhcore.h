@@ -253,6 +253,19 @@ int bh_blosc_filter(bh_ctx* ctx, const void* src, void* dst, uint64_t nbytes, ui
 uint64_t bh_blosc_lz4_bound(uint32_t nframes, uint32_t cbytes, uint32_t blocksize);
 int bh_blosc_lz4_compress(bh_ctx* ctx, const void* src, uint32_t nframes, uint32_t cbytes, uint32_t blocksize, uint32_t typesize,
                           int shuffle_mode, void* out, uint64_t* foff);
+/* The same for the container's zstd inner codec, the one iohub stores use by default: every block becomes one complete zstd
+ * frame (RFC 8878: single segment, content size recorded, no checksum, no dictionary — what c-blosc's ZSTD_compressCCtx per
+ * block gives), encoded by one wavefront: greedy matches (offsets <= 65535), Huffman-coded literals, sequences in the
+ * predefined FSE tables; a block whose frame is not smaller is stored raw.  Same arguments, same packing and the same
+ * contract as the lz4 pair; frame flags 0x10 | 4 << 5 | shuffle bits.  Any zstd decoder reads the blocks.  Does not
+ * synchronise. */
+uint64_t bh_blosc_zstd_bound(uint32_t nframes, uint32_t cbytes, uint32_t blocksize);
+int bh_blosc_zstd_compress(bh_ctx* ctx, const void* src, uint32_t nframes, uint32_t cbytes, uint32_t blocksize, uint32_t typesize,
+                           int shuffle_mode, void* out, uint64_t* foff);
+/* The host form of that encoder (no GPU, no context; the same source compiled with one lane): src[0, n) -> one zstd frame in
+ * dst[0, *csize), or, when the frame would not be smaller than n, the n bytes themselves (*csize == n: the container's mark
+ * for a stored block).  1 <= n <= 2^30, cap >= n. */
+int bh_host_zstd_compress(const void* src, uint64_t n, void* dst, uint64_t cap, uint64_t* csize);
 /* LZ4 streams back to bytes on the device: stream i is csize[i] bytes at src + soff[i] and decodes to dlen[i] bytes at
  * dst + doff[i] (device arrays of nstreams entries; csize == dlen marks a stored stream).  The caller reads the Blosc frame's
  * block table on the host — a block is one stream, or `typesize` streams when its writer split it (c-blosc 1.21 splits lz4

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Chunk-codec timings: a uint16 camera volume in an iohub-style Blosc (zstd level 1, bit shuffle) store, host path
 (NumPy permutation on the I/O threads) against the device path (bh_blosc_filter / bh_blosc_unfilter), both zarr versions,
-plus the kernels alone.    python tools/codec_bench.py [--shape 256 1024 1024]"""
+plus the kernels alone (permutations, the lz4 and zstd block codecs).    python tools/codec_bench.py [--shape 256 1024 1024]"""
 import argparse, json, sys, tempfile, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
@@ -104,4 +104,15 @@ t, _ = timed(lambda: codecs.blosc_decode_frames_device(frames, back, [i * cbytes
 assert torch.equal(back, filt)
 out["kernel_lz4_decompress_volume_incl_upload"] = {"ms": round(t * 1e3, 2), "GBps_out": round(src.numel() / t / 1e9, 1),
                                                    "note": "the volume's frames in one upload and one launch (read_volume_device)"}
+# zstd on the device (csrc/zstd_enc.hip): the same permuted volume -> Blosc-zstd frames, read back by the device decoder
+zpacked, zoffs = codecs.blosc_zstd_compress_device(filt, nchunks, cbytes, 256 << 10, 2, 2)
+t, (zpacked, zoffs) = timed(lambda: codecs.blosc_zstd_compress_device(filt, nchunks, cbytes, 256 << 10, 2, 2), reps=3)
+out["kernel_zstd_compress_frames"] = {"ms": round(t * 1e3, 2), "GBps_in": round(src.numel() / t / 1e9, 1), "ratio": round(zoffs[-1] / src.numel(), 3)}
+zhost = zpacked[: zoffs[-1]].cpu().numpy()
+zframes = [zhost[zoffs[i]: zoffs[i + 1]].tobytes() for i in range(nchunks)]
+back.zero_()
+t, _ = timed(lambda: codecs.blosc_decode_frames_device(zframes, back, [i * cbytes for i in range(nchunks)]), reps=3)
+assert torch.equal(back, filt)
+out["kernel_zstd_decompress_volume_incl_upload"] = {"ms": round(t * 1e3, 2), "GBps_out": round(src.numel() / t / 1e9, 1),
+                                                    "note": "frames written by the device encoder"}
 print(json.dumps(out, indent=1))
