@@ -62,6 +62,7 @@ SIGNATURES = {
     "bh_blosc_zstd_bound": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_blosc_zstd_compress": (_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _int, _vp, _vp]),
     "bh_host_zstd_compress": (_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "bh_host_zstd_decompress": (_int, [_vp, C.c_uint64, _vp, C.c_uint64]),
     "bh_lz4_decompress_streams": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "bh_zstd_decompress_streams": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp]),
     "bh_host_blosc_unfilter": (_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _int]),

@@ -31,7 +31,8 @@ INCLUDES = {"fftconv.hip": _FC, "fftconv_col.hip": _FC, "fftconv_xtile.hip": _FC
             "fftconv_colreg.hip": _FC + ("fftconv_xw.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"),
             "deconv.hip": ("fftconv.hpp",), "invtf.hip": ("fftconv.hpp",), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
             "deskew.hip": ("deskew_geom.hpp", "deskew_rows.inc"), "host_deskew.hip": ("deskew_geom.hpp",), "lz4.hip": ("blosc_frame.hpp",),
-            "zstd.hip": ("zstd_frame.inc", "zstd_block.inc", "zstd_tables.inc"), "zstd_enc.hip": ("zstd_enc.inc", "zstd_tables.inc", "blosc_frame.hpp")}
+            "zstd.hip": ("zstd_lanes.inc", "zstd_format.inc", "zstd_frame.inc", "zstd_block.inc", "blosc_frame.hpp"),
+            "zstd_enc.hip": ("zstd_lanes.inc", "zstd_format.inc", "zstd_enc.inc", "blosc_frame.hpp")}
 
 
 def needs_build() -> bool:

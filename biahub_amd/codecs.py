@@ -474,6 +474,22 @@ def zstd_compress_host(buf) -> bytes:
     return dst[: csize.value].tobytes()
 
 
+def zstd_decompress_host(buf, nbytes: int) -> np.ndarray:
+    """The ``nbytes`` bytes of one stream from the library's OWN decoder on the CPU (``bh_host_zstd_decompress``: the source of
+    the device decoder compiled with one lane).  A stream of ``nbytes`` bytes is a stored one and comes back as it is; anything
+    else must be one complete zstd frame of that content size (``ValueError`` when it is corrupt).  ``zstd_decompress``
+    (libzstd) is what the host readers use; this one exists to test and debug the decoder."""
+    import ctypes
+
+    from . import _lib
+
+    raw = np.ascontiguousarray(np.frombuffer(memoryview(buf), np.uint8))
+    dst = np.empty(max(int(nbytes), 1), np.uint8)
+    src = raw if raw.size else np.zeros(1, np.uint8)
+    _lib.check(_lib.load().bh_host_zstd_decompress(src.ctypes.data_as(ctypes.c_void_p), raw.size, dst.ctypes.data_as(ctypes.c_void_p), int(nbytes)))
+    return dst[: int(nbytes)]
+
+
 _DEVICE_DECODERS = {"lz4": "bh_lz4_decompress_streams", "zstd": "bh_zstd_decompress_streams"}  # csrc/lz4.hip, csrc/zstd.hip
 
 

@@ -6,8 +6,9 @@
 //   byte shuffle: byte j of element i sits at j n + i; the bytes % typesize tail is unpermuted;
 //   bit shuffle : bit k of byte j of element i sits at bit i % 8 of byte (8 j + k) n / 8 + i / 8 — only when n % 8 == 0,
 //                 otherwise c-blosc 1.x stores the block unpermuted.
-// The entropy decoder (zstd) runs on host cores; its output is uploaded still permuted and un-permuted here, so the
-// strided byte gather happens at HBM rate instead of on a core.  Pure byte movement: bit-exact by construction, checked
+// The block codecs (csrc/lz4.hip, csrc/zstd.hip; on the host only with BH_LZ4_DEVICE=0 / BH_ZSTD_DEVICE=0) leave their output
+// on the device still permuted and it is un-permuted here, so the strided byte gather happens at HBM rate instead of on a
+// core.  Pure byte movement: bit-exact by construction, checked
 // against the NumPy restatement and against streams of the real library (tests/test_gpu_parity.py).
 //
 // Work item = G consecutive elements of one block; a 256-thread workgroup takes 256 consecutive items, so every plane is

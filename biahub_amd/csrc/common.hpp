@@ -105,6 +105,10 @@ struct bh_ctx {
 
 namespace bh {
 
+// grid of a kernel whose persistent wavefronts take one of n items (blocks, streams) at a time, `waves` wavefronts per workgroup
+inline int wave_grid(const bh_ctx* ctx, uint64_t n, int waves) {
+    return (int)std::min<uint64_t>((n + waves - 1) / waves, (uint64_t)ctx->num_cus * 2);
+}
 // returns a device buffer of at least `bytes`, cached under `name`
 int get_scratch(bh_ctx* ctx, const char* name, size_t bytes, void** out);
 int free_scratch(bh_ctx* ctx, const char* name);

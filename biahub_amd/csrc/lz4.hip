@@ -35,6 +35,7 @@ constexpr int MFLIMIT = 12, LASTLITERALS = 5, MINMATCH = 4;
 using blosc_frame::ld32;
 using blosc_frame::st32;
 using blosc_frame::wave_copy;
+using blosc_frame::wave_extend;
 
 // a length >= 15 continues behind its nibble as bytes that add up to (len - 15): 255, 255, ..., rest
 __device__ __forceinline__ unsigned ext_bytes(unsigned len) { return len >= 15 ? (len - 15) / 255 + 1 : 0; }
@@ -89,30 +90,7 @@ __global__ __launch_bounds__(64 * WAVES) void compress_kernel(const uint8_t* __r
                 const int first = __builtin_ctzll(m);
                 const unsigned mp = ip + first;
                 const unsigned mc = (unsigned)__builtin_amdgcn_readlane((int)cand, first);
-                // extend: dwords 1.. of the match, 256 bytes per step
-                unsigned len = MINMATCH;
-                for (;;) {
-                    const unsigned q = mp + len + 4 * lane;
-                    const bool in_range = q + 4 <= matchlimit;
-                    const unsigned a = in_range ? ld32(in + q) : 0u, c = in_range ? ld32(in + (mc + len + 4 * lane)) : 1u;
-                    const unsigned x = a ^ c;
-                    const unsigned long long neq = __ballot(x != 0u || !in_range);
-                    if (neq == 0ull) {
-                        len += 256;
-                        continue;
-                    }
-                    const int fl = __builtin_ctzll(neq);
-                    len += 4 * fl;
-                    // the lane that stopped the run: a differing byte inside its dword, or the end of the comparable range
-                    const unsigned qf = mp + len;
-                    if (qf + 4 <= matchlimit) {
-                        const unsigned xf = (unsigned)__builtin_amdgcn_readlane((int)x, fl);
-                        len += (unsigned)__builtin_ctz(xf) >> 3;
-                    } else {
-                        while (mp + len < matchlimit && in[mp + len] == in[mc + len]) ++len;  // at most three bytes (uniform loop)
-                    }
-                    break;
-                }
+                const unsigned len = wave_extend(in, mp, mc, matchlimit, lane);  // dwords 1.. of the match
                 // sequence: token, literal length bytes, literals, offset, match length bytes
                 const unsigned lit = mp - anchor, ml = len - MINMATCH;
                 const unsigned need = 1 + ext_bytes(lit) + lit + 2 + ext_bytes(ml);
@@ -330,40 +308,21 @@ __global__ __launch_bounds__(64 * D_WAVES) void decompress_kernel(const uint8_t*
 
 extern "C" {
 
-// src: nframes * cbytes permuted bytes (chunks back to back); out: packed Blosc frames; foff (device, nframes + 1 uint64): the
-// frames' offsets in `out` and the total.  out must hold bh_blosc_lz4_bound(nframes, cbytes, blocksize) bytes.
-uint64_t bh_blosc_lz4_bound(uint32_t nframes, uint32_t cbytes, uint32_t blocksize) {
-    const uint64_t nb = (cbytes + (uint64_t)blocksize - 1) / blocksize;
-    return (uint64_t)nframes * ((16 + 8 * nb + cbytes + 15) & ~(uint64_t)15);
-}
+// The lz4 writer's pair of the container: contract in blosc_frame::bound / compress_frames.
+uint64_t bh_blosc_lz4_bound(uint32_t nframes, uint32_t cbytes, uint32_t blocksize) { return bh::blosc_frame::bound(nframes, cbytes, blocksize); }
 
 int bh_blosc_lz4_compress(bh_ctx* ctx, const void* src, uint32_t nframes, uint32_t cbytes, uint32_t blocksize, uint32_t typesize,
                           int shuffle_mode, void* out, uint64_t* foff) {
     using namespace bh;
-    BH_REQUIRE(ctx && src && out && foff, "NULL argument");
-    BH_REQUIRE(nframes > 0 && cbytes >= 128 && blocksize >= 128 && blocksize <= (1u << 30), "invalid frame geometry");
-    BH_REQUIRE(typesize >= 1 && typesize <= 255, "invalid typesize %u", typesize);
-    BH_CHECK_HIP(hipSetDevice(ctx->device));
-    const uint32_t nb = (uint32_t)(((uint64_t)cbytes + blocksize - 1) / blocksize);
-    BH_REQUIRE((uint64_t)nframes * nb < (1ull << 31), "too many blocks");
-    const uint32_t nblocks = nframes * nb;
-    const uint64_t slot = ((uint64_t)blocksize + 15) & ~(uint64_t)15;
-    uint8_t* slots;
-    uint32_t *sizes, *bstarts, *fbytes;
-    BH_TRY(get_scratch(ctx, "lz4_slots", (uint64_t)nblocks * slot, (void**)&slots));
-    BH_TRY(get_scratch(ctx, "lz4_sizes", (uint64_t)nblocks * 4, (void**)&sizes));
-    BH_TRY(get_scratch(ctx, "lz4_bstarts", (uint64_t)nblocks * 4, (void**)&bstarts));
-    BH_TRY(get_scratch(ctx, "lz4_fbytes", (uint64_t)nframes * 4, (void**)&fbytes));
-    hipStream_t s = ctx->stream;
-    const int grid = (int)std::min<uint64_t>(((uint64_t)nblocks + lz4::WAVES - 1) / lz4::WAVES, (uint64_t)ctx->num_cus * 2);
     // every block of every frame in one launch (frame by frame, a store with 60-MB chunks kept 30 CUs busy per launch: 35
     // launches of 5.7 ms for a 2-GB volume)
-    hipLaunchKernelGGL(lz4::compress_kernel, dim3(grid), dim3(64 * lz4::WAVES), 0, s, (const uint8_t*)src, cbytes, (uint32_t)nb, blocksize, slots,
-                       slot, sizes, nblocks);
-    const uint32_t flags = 0x10u | (1u << 5) | (shuffle_mode == BH_BLOSC_SHUFFLE ? 0x1u : (shuffle_mode == BH_BLOSC_BITSHUFFLE ? 0x4u : 0u));
-    blosc_frame::launch_frame_assembly(s, slots, slot, sizes, bstarts, fbytes, nb, nframes, cbytes, blocksize, typesize, flags, (uint8_t*)out, foff);
-    BH_CHECK_HIP(hipGetLastError());
-    return BH_OK;
+    auto launch = [&](uint8_t* slots, uint64_t slot, uint32_t* sizes, uint32_t nb, uint32_t nblocks) -> int {
+        hipLaunchKernelGGL(lz4::compress_kernel, dim3(wave_grid(ctx, nblocks, lz4::WAVES)), dim3(64 * lz4::WAVES), 0, ctx->stream,
+                           (const uint8_t*)src, cbytes, nb, blocksize, slots, slot, sizes, nblocks);
+        return BH_OK;
+    };
+    return blosc_frame::compress_frames(ctx, src, nframes, cbytes, blocksize, typesize, shuffle_mode, 1, "lz4", ((uint64_t)blocksize + 15) & ~(uint64_t)15,
+                                        launch, out, foff);
 }
 
 // LZ4 streams back to bytes on the device: stream i = csize[i] bytes at src + soff[i] -> dlen[i] bytes at dst + doff[i] (four
@@ -382,7 +341,7 @@ int bh_lz4_decompress_streams(bh_ctx* ctx, const void* src, const uint64_t* soff
     BH_CHECK_HIP(hipMemsetAsync(status, 0, sizeof(int), s));
     const size_t lds = (size_t)lz4::D_WAVES * (lz4::D_RING + lz4::D_STAGE);  // 80 KiB: two workgroups per CU
     BH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lz4::decompress_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int grid = (int)std::min<uint64_t>(((uint64_t)nstreams + lz4::D_WAVES - 1) / lz4::D_WAVES, (uint64_t)ctx->num_cus * 2);
+    const int grid = wave_grid(ctx, nstreams, lz4::D_WAVES);
     hipLaunchKernelGGL(lz4::decompress_kernel, dim3(grid), dim3(64 * lz4::D_WAVES), lds, s, (const uint8_t*)src, soff, csize, doff, dlen,
                        nstreams, (uint8_t*)dst, status);
     BH_CHECK_HIP(hipGetLastError());

@@ -8,41 +8,44 @@
 // per-wave global scratch of one block (128 KiB); then all 64 lanes copy the batch's literals (a running sum of LL and ML gives
 // every output position) and run its matches in order, reading the frame's own output back from global memory after waiting
 // for this wave's stores.  Every lane hand-off through LDS goes through a wavefront fence and barrier.
+// The decoder is compiled twice, under the two macro sets of zstd_lanes.inc: for the wavefront (the kernel below) and with one
+// lane for the host (bh_host_zstd_decompress: no GPU, for tests and debugging only).
 #include "common.hpp"
 
-#define ZS_CONST __constant__
-#define ZS_LANE_DECL const int lane = (int)(threadIdx.x & 63u)
-#define ZS_SERIAL if (lane == 0)
-#define ZS_LANES
-#define ZS_SYNC()                                              \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
+#include <cstring>
+#include <vector>
 
 namespace bh {
 namespace zstd {
 
-// this wave's earlier global stores have landed (a match or a literal read-back may reach them)
-__device__ __forceinline__ void zs_wait_own_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// a byte this wave wrote earlier: read past the vector cache
-__device__ __forceinline__ uint8_t zs_load_own(const uint8_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
+namespace dev {
+#define ZS_TARGET_DEVICE
+#include "zstd_lanes.inc"
 #include "zstd_frame.inc"
+#define ZS_TARGET_END
+#include "zstd_lanes.inc"
+}  // namespace dev
 
-constexpr int WAVES = 4;  // wavefronts per workgroup; 4 x sizeof(zs::Lds) of static LDS
+namespace host {
+#define ZS_TARGET_HOST
+#include "zstd_lanes.inc"
+#include "zstd_frame.inc"
+#define ZS_TARGET_END
+#include "zstd_lanes.inc"
+}  // namespace host
+
+constexpr int WAVES = 4;  // wavefronts per workgroup; 4 x sizeof(dev::zs::Lds) of static LDS
 
 __global__ __launch_bounds__(64 * WAVES) void decompress_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ soff,
                                                                const uint32_t* __restrict__ csize, const uint64_t* __restrict__ doff,
                                                                const uint32_t* __restrict__ dlen, uint32_t nstreams,
                                                                uint8_t* __restrict__ dst, uint8_t* __restrict__ scratch,
                                                                unsigned* __restrict__ status) {
-    __shared__ zs::Lds lds[WAVES];
+    __shared__ dev::zs::Lds lds[WAVES];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    zs::Lds* L = &lds[wave];
-    uint8_t* lit = scratch + (uint64_t)(blockIdx.x * WAVES + wave) * zs::LIT_SCRATCH;
+    dev::zs::Lds* L = &lds[wave];
+    uint8_t* lit = scratch + (uint64_t)(blockIdx.x * WAVES + wave) * dev::zs::LIT_SCRATCH;
     for (uint32_t b = blockIdx.x * WAVES + wave; b < nstreams; b += gridDim.x * WAVES) {
         const uint8_t* in = src + soff[b];
         const uint32_t cs = csize[b], n = dlen[b];
@@ -51,7 +54,7 @@ __global__ __launch_bounds__(64 * WAVES) void decompress_kernel(const uint8_t* _
             for (uint32_t j = lane; j < n; j += 64) out[j] = in[j];
             continue;
         }
-        if (!zs::decode_frame(in, cs, out, n, lit, L) && lane == 0) atomicMin(status, b);
+        if (!dev::zs::decode_frame(in, cs, out, n, lit, L) && lane == 0) atomicMin(status, b);
     }
 }
 
@@ -69,11 +72,11 @@ int bh_zstd_decompress_streams(bh_ctx* ctx, const void* src, const uint64_t* sof
     BH_REQUIRE(ctx && src && soff && csize && doff && dlen && dst, "NULL argument");
     BH_REQUIRE(nstreams > 0, "no streams");
     BH_CHECK_HIP(hipSetDevice(ctx->device));
-    const int grid = (int)std::min<uint64_t>(((uint64_t)nstreams + zstd::WAVES - 1) / zstd::WAVES, (uint64_t)ctx->num_cus * 2);
+    const int grid = wave_grid(ctx, nstreams, zstd::WAVES);
     unsigned* status;
     uint8_t* scratch;
     BH_TRY(get_scratch(ctx, "zstd_status", sizeof(unsigned), (void**)&status));
-    BH_TRY(get_scratch(ctx, "zstd_literals", (uint64_t)grid * zstd::WAVES * zstd::zs::LIT_SCRATCH, (void**)&scratch));
+    BH_TRY(get_scratch(ctx, "zstd_literals", (uint64_t)grid * zstd::WAVES * zstd::dev::zs::LIT_SCRATCH, (void**)&scratch));
     hipStream_t s = ctx->stream;
     BH_CHECK_HIP(hipMemsetAsync(status, 0xff, sizeof(unsigned), s));
     hipLaunchKernelGGL(zstd::decompress_kernel, dim3(grid), dim3(64 * zstd::WAVES), 0, s, (const uint8_t*)src, soff, csize, doff, dlen,
@@ -83,6 +86,23 @@ int bh_zstd_decompress_streams(bh_ctx* ctx, const void* src, const uint64_t* sof
     BH_CHECK_HIP(hipMemcpyAsync(&h, status, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     BH_CHECK_HIP(hipStreamSynchronize(s));
     BH_REQUIRE(h == 0xffffffffu, "corrupt zstd stream %u", h);
+    return BH_OK;
+}
+
+// The decoder on the host (no GPU, no context), one stream under the device entry's contract: src[0, csize) -> dst[0, n).
+// csize == n: a stored stream; else one complete frame of exactly n bytes.  BH_ERR_INVALID on a corrupt frame.
+int bh_host_zstd_decompress(const void* src, uint64_t csize, void* dst, uint64_t n) {
+    using namespace bh;
+    namespace zs = zstd::host::zs;
+    BH_REQUIRE(src && dst, "NULL argument");
+    BH_REQUIRE(csize < (1ull << 31) && n < (1ull << 31), "invalid length");
+    if (csize == n) {
+        std::memcpy(dst, src, n);
+        return BH_OK;
+    }
+    std::vector<zs::Lds> lds(1);
+    std::vector<uint8_t> lit(zs::LIT_SCRATCH);
+    BH_REQUIRE(zs::decode_frame((const uint8_t*)src, (uint32_t)csize, (uint8_t*)dst, (uint32_t)n, lit.data(), &lds[0]), "corrupt zstd stream");
     return BH_OK;
 }
 

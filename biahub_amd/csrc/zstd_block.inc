@@ -2,11 +2,11 @@
 // zstd_frame.inc inside namespace zs.
 
 // FSE mode of one of LL / OF / ML at in[ip, lim) (§3.1.1.3.2.2): the table in L->tab + TAB_OFF[t]
-__device__ bool seq_table(const uint8_t* in, uint32_t& ip, uint32_t lim, int mode, int t, Lds* L, Ctl* c) {
+ZS_FN bool seq_table(const uint8_t* in, uint32_t& ip, uint32_t lim, int mode, int t, Lds* L, Ctl* c) {
     uint32_t* tab = L->tab + TAB_OFF[t];
     if (mode == 0) {  // predefined
         if (!fse_predefined(L, t)) return false;
-        c->tab_log[t] = t == T_OF ? 5 : 6;
+        c->tab_log[t] = (uint32_t)predefined(t).log;
     } else if (mode == 1) {  // RLE: one symbol
         if (ip >= lim) return false;
         const uint32_t s = in[ip++];
@@ -26,14 +26,14 @@ __device__ bool seq_table(const uint8_t* in, uint32_t& ip, uint32_t lim, int mod
 }
 
 // one literal of the block (uniform kind)
-__device__ __forceinline__ uint8_t lit_at(const uint8_t* in, const uint8_t* lit, uint32_t kind, uint32_t src, uint32_t byte, uint32_t i) {
+ZS_FN inline uint8_t lit_at(const uint8_t* in, const uint8_t* lit, uint32_t kind, uint32_t src, uint32_t byte, uint32_t i) {
     if (kind == 0) return in[src + i];
     if (kind == 1) return (uint8_t)byte;
     return zs_load_own(lit + i);
 }
 
 // block content in[ip, bend) -> out[c->op, ...)
-__device__ bool decode_block(const uint8_t* __restrict__ in, uint32_t ip0, uint32_t bend, uint8_t* __restrict__ out, uint32_t n,
+ZS_FN bool decode_block(const uint8_t* __restrict__ in, uint32_t ip0, uint32_t bend, uint8_t* __restrict__ out, uint32_t n,
                              uint8_t* __restrict__ lit, Lds* L) {
     ZS_LANE_DECL;
     Ctl* c = &L->c;
@@ -136,33 +136,29 @@ __device__ bool decode_block(const uint8_t* __restrict__ in, uint32_t ip0, uint3
     if (c->lit_kind == 2) {
         if (c->huf_new) {  // the decode table: symbol s owns 2^(maxbits - nbits) consecutive entries from hstart[s]
             const uint32_t nsym = c->huf_nsym, mb = c->huf_bits;
-            ZS_LANES {
-                for (uint32_t s = lane; s < nsym; s += 64) {
-                    const uint32_t w = L->hw[s];
-                    if (!w) continue;
-                    const uint32_t nb = mb + 1 - w, st = L->hstart[s], cnt = 1u << (mb - nb);
-                    for (uint32_t j = 0; j < cnt; ++j) L->huf[st + j] = (uint16_t)(s | (nb << 8));
-                }
+            for (uint32_t s = lane; s < nsym; s += ZS_WIDTH) {
+                const uint32_t w = L->hw[s];
+                if (!w) continue;
+                const uint32_t nb = mb + 1 - w, st = L->hstart[s], cnt = 1u << (mb - nb);
+                for (uint32_t j = 0; j < cnt; ++j) L->huf[st + j] = (uint16_t)(s | (nb << 8));
             }
             ZS_SYNC();
         }
         const uint32_t nstr = c->nstr, mb = c->huf_bits;
-        ZS_LANES {  // one lane per Huffman stream
-            if ((uint32_t)lane < nstr) {
-                BitBack hb;
-                const uint32_t cnt = c->hs_cnt[lane];
-                uint8_t* o = lit + c->hs_out[lane];
-                bool ok = hb.init(in + c->hs_off[lane], c->hs_len[lane]);
-                if (ok) {
-                    for (uint32_t i = 0; i < cnt; ++i) {
-                        const uint32_t e = L->huf[hb.peek((int)mb)];
-                        o[i] = (uint8_t)(e & 0xffu);
-                        hb.off -= (int32_t)(e >> 8);
-                    }
-                    ok = hb.off == 0;
+        for (uint32_t k = lane; k < nstr; k += ZS_WIDTH) {  // one lane per Huffman stream
+            BitBack hb;
+            const uint32_t cnt = c->hs_cnt[k];
+            uint8_t* o = lit + c->hs_out[k];
+            bool ok = hb.init(in + c->hs_off[k], c->hs_len[k]);
+            if (ok) {
+                for (uint32_t i = 0; i < cnt; ++i) {
+                    const uint32_t e = L->huf[hb.peek((int)mb)];
+                    o[i] = (uint8_t)(e & 0xffu);
+                    hb.off -= (int32_t)(e >> 8);
                 }
-                c->herr[lane] = ok ? 0u : 1u;
+                ok = hb.off == 0;
             }
+            c->herr[k] = ok ? 0u : 1u;
         }
         zs_wait_own_stores();  // the literals are read back by every lane
         ZS_SYNC();
@@ -278,17 +274,15 @@ __device__ bool decode_block(const uint8_t* __restrict__ in, uint32_t ip0, uint3
         nleft -= nb;
         {  // literals of the batch, all lanes over all of them: byte t belongs to the last sequence whose literals start <= t
             const uint32_t lit0 = L->b_lit[0], tot = L->b_lit[nb - 1] + L->b_ll[nb - 1] - lit0;
-            ZS_LANES {
-                for (uint32_t t = lane; t < tot; t += 64) {
-                    const uint32_t q = lit0 + t;
-                    uint32_t lo = 0, hi = nb - 1;
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi + 1) >> 1;
-                        if (L->b_lit[mid] <= q) lo = mid;
-                        else hi = mid - 1;
-                    }
-                    out[L->b_out[lo] + (q - L->b_lit[lo])] = lit_at(in, lit, lkind, lsrc, lbyte, q);
+            for (uint32_t t = lane; t < tot; t += ZS_WIDTH) {
+                const uint32_t q = lit0 + t;
+                uint32_t lo = 0, hi = nb - 1;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi + 1) >> 1;
+                    if (L->b_lit[mid] <= q) lo = mid;
+                    else hi = mid - 1;
                 }
+                out[L->b_out[lo] + (q - L->b_lit[lo])] = lit_at(in, lit, lkind, lsrc, lbyte, q);
             }
         }
         zs_wait_own_stores();
@@ -303,17 +297,15 @@ __device__ bool decode_block(const uint8_t* __restrict__ in, uint32_t ip0, uint3
                 zs_wait_own_stores();
                 dirty = 0xffffffffu;
             }
-            ZS_LANES {
-                if (off >= ml) {
-                    for (uint32_t j = lane; j < ml; j += 64) out[p + j] = zs_load_own(out + from + j);
-                } else {
-                    uint32_t r = (uint32_t)lane % off;
-                    const uint32_t step = 64u % off;
-                    for (uint32_t j = lane; j < ml; j += 64) {
-                        out[p + j] = zs_load_own(out + from + r);
-                        r += step;
-                        r -= r >= off ? off : 0u;
-                    }
+            if (off >= ml) {
+                for (uint32_t j = lane; j < ml; j += ZS_WIDTH) out[p + j] = zs_load_own(out + from + j);
+            } else {
+                uint32_t r = lane % off;
+                const uint32_t step = ZS_WIDTH % off;
+                for (uint32_t j = lane; j < ml; j += ZS_WIDTH) {
+                    out[p + j] = zs_load_own(out + from + r);
+                    r += step;
+                    r -= r >= off ? off : 0u;
                 }
             }
             if (ml > 0 && p < dirty) dirty = p;
@@ -336,9 +328,7 @@ __device__ bool decode_block(const uint8_t* __restrict__ in, uint32_t ip0, uint3
     if (c->err) return false;
     {
         const uint32_t top = c->tail_op, tl = c->tail_lit, tn = c->tail_n;
-        ZS_LANES {
-            for (uint32_t t = lane; t < tn; t += 64) out[top + t] = lit_at(in, lit, lkind, lsrc, lbyte, tl + t);
-        }
+        for (uint32_t t = lane; t < tn; t += ZS_WIDTH) out[top + t] = lit_at(in, lit, lkind, lsrc, lbyte, tl + t);
     }
     return true;
 }

@@ -17,80 +17,19 @@ namespace bh {
 namespace zstd_enc {
 
 namespace dev {
-
-#define ZS_FN __device__
-#define ZS_CONST __constant__
-#define ZS_LANE_DECL const uint32_t lane = threadIdx.x & 63u
-#define ZS_SERIAL if (lane == 0)
-#define ZS_WIDTH 64u
-#define ZS_SYNC()                                              \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
-#define ZSE_DEVICE 1
-
-// this wave's earlier global stores have landed (the literal scratch is read back by other lanes)
-__device__ __forceinline__ void zs_wait_own_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// a byte this wave wrote earlier: read past the vector cache
-__device__ __forceinline__ uint8_t zs_load_own(const uint8_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// exclusive prefix sum of v over the wavefront's lanes (all active); *total: the sum
-__device__ __forceinline__ uint32_t zs_scan_excl(uint32_t v, uint32_t* total) {
-    const int lane = (int)(threadIdx.x & 63u);
-    uint32_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    *total = (uint32_t)__shfl((int)incl, 63, 64);
-    return incl - v;
-}
-__device__ __forceinline__ void zs_atomic_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
-__device__ __forceinline__ void zs_atomic_inc(uint32_t* p) { atomicAdd(p, 1u); }
-
+#define ZS_TARGET_DEVICE
+#include "zstd_lanes.inc"
 #include "zstd_enc.inc"
-
-#undef ZS_FN
-#undef ZS_CONST
-#undef ZS_LANE_DECL
-#undef ZS_SERIAL
-#undef ZS_WIDTH
-#undef ZS_SYNC
-#undef ZSE_DEVICE
-
+#define ZS_TARGET_END
+#include "zstd_lanes.inc"
 }  // namespace dev
 
 namespace host {
-
-#define ZS_FN
-#define ZS_CONST static const
-#define ZS_LANE_DECL const uint32_t lane = 0
-#define ZS_SERIAL if (lane == 0)
-#define ZS_WIDTH 1u
-#define ZS_SYNC() \
-    do {          \
-    } while (0)
-
-static inline void zs_wait_own_stores() {}
-static inline uint8_t zs_load_own(const uint8_t* p) { return *p; }
-static inline uint32_t zs_scan_excl(uint32_t v, uint32_t* total) {
-    *total = v;
-    return 0;
-}
-static inline void zs_atomic_or(uint32_t* p, uint32_t v) { *p |= v; }
-static inline void zs_atomic_inc(uint32_t* p) { ++*p; }
-
+#define ZS_TARGET_HOST
+#include "zstd_lanes.inc"
 #include "zstd_enc.inc"
-
-#undef ZS_FN
-#undef ZS_CONST
-#undef ZS_LANE_DECL
-#undef ZS_SERIAL
-#undef ZS_WIDTH
-#undef ZS_SYNC
-
+#define ZS_TARGET_END
+#include "zstd_lanes.inc"
 }  // namespace host
 
 constexpr int WAVES = 4;  // wavefronts per workgroup; 4 x sizeof(zse::Work) of dynamic LDS (66 KiB: two workgroups per CU)
@@ -133,48 +72,28 @@ static uint64_t slot_bytes(uint32_t blocksize) { return (dev::zse::frame_bound(b
 
 extern "C" {
 
-// Upper bound of the packed frames.  A block never takes more than its own length in a frame (a zstd frame that is not smaller
-// is replaced by the raw bytes), so a frame is at most 16 (header) + nb * (4 (start) + 4 (size)) + cbytes bytes, rounded up to
-// the 16-byte alignment of the next frame: the same bound as the lz4 writer's.
-uint64_t bh_blosc_zstd_bound(uint32_t nframes, uint32_t cbytes, uint32_t blocksize) {
-    const uint64_t nb = (cbytes + (uint64_t)blocksize - 1) / blocksize;
-    return (uint64_t)nframes * ((16 + 8 * nb + cbytes + 15) & ~(uint64_t)15);
-}
+// The zstd writer's pair of the container: contract in blosc_frame::bound / compress_frames.
+uint64_t bh_blosc_zstd_bound(uint32_t nframes, uint32_t cbytes, uint32_t blocksize) { return bh::blosc_frame::bound(nframes, cbytes, blocksize); }
 
-// src: nframes * cbytes permuted bytes (chunks back to back); out: packed Blosc frames (inner codec zstd); foff (device,
-// nframes + 1 uint64): the frames' offsets in `out` and the total.  out must hold bh_blosc_zstd_bound(nframes, cbytes, blocksize).
 int bh_blosc_zstd_compress(bh_ctx* ctx, const void* src, uint32_t nframes, uint32_t cbytes, uint32_t blocksize, uint32_t typesize,
                            int shuffle_mode, void* out, uint64_t* foff) {
     using namespace bh;
-    BH_REQUIRE(ctx && src && out && foff, "NULL argument");
-    BH_REQUIRE(nframes > 0 && cbytes >= 128 && blocksize >= 128 && blocksize <= (1u << 30), "invalid frame geometry");
-    BH_REQUIRE(typesize >= 1 && typesize <= 255, "invalid typesize %u", typesize);
-    BH_CHECK_HIP(hipSetDevice(ctx->device));
-    const uint32_t nb = (uint32_t)(((uint64_t)cbytes + blocksize - 1) / blocksize);
-    BH_REQUIRE((uint64_t)nframes * nb < (1ull << 31), "too many blocks");
-    const uint32_t nblocks = nframes * nb;
-    const uint64_t slot = zstd_enc::slot_bytes(blocksize);
-    const int grid = (int)std::min<uint64_t>(((uint64_t)nblocks + zstd_enc::WAVES - 1) / zstd_enc::WAVES, (uint64_t)ctx->num_cus * 2);
-    uint8_t *slots, *lits;
-    uint64_t* seqs;
-    uint32_t *sizes, *bstarts, *fbytes;
-    BH_TRY(get_scratch(ctx, "zstd_enc_slots", (uint64_t)nblocks * slot, (void**)&slots));
-    BH_TRY(get_scratch(ctx, "zstd_enc_sizes", (uint64_t)nblocks * 4, (void**)&sizes));
-    BH_TRY(get_scratch(ctx, "zstd_enc_bstarts", (uint64_t)nblocks * 4, (void**)&bstarts));
-    BH_TRY(get_scratch(ctx, "zstd_enc_fbytes", (uint64_t)nframes * 4, (void**)&fbytes));
-    // per wave of the grid: the literals and the sequences of one zstd block
-    BH_TRY(get_scratch(ctx, "zstd_enc_literals", (uint64_t)grid * zstd_enc::WAVES * zstd_enc::dev::zse::BLOCK_MAX, (void**)&lits));
-    BH_TRY(get_scratch(ctx, "zstd_enc_sequences", (uint64_t)grid * zstd_enc::WAVES * zstd_enc::dev::zse::MAXSEQ * 8, (void**)&seqs));
-    hipStream_t s = ctx->stream;
-    BH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(zstd_enc::compress_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)zstd_enc::LDS_BYTES));
-    hipLaunchKernelGGL(zstd_enc::compress_kernel, dim3(grid), dim3(64 * zstd_enc::WAVES), zstd_enc::LDS_BYTES, s, (const uint8_t*)src, cbytes, nb, blocksize, slots,
-                       slot, sizes, nblocks, lits, seqs);
-    // flags: blocks never split, inner codec zstd (4), the permutation the caller applied
-    const uint32_t flags = 0x10u | (4u << 5) | (shuffle_mode == BH_BLOSC_SHUFFLE ? 0x1u : (shuffle_mode == BH_BLOSC_BITSHUFFLE ? 0x4u : 0u));
-    blosc_frame::launch_frame_assembly(s, slots, slot, sizes, bstarts, fbytes, nb, nframes, cbytes, blocksize, typesize, flags, (uint8_t*)out, foff);
-    BH_CHECK_HIP(hipGetLastError());
-    return BH_OK;
+    namespace zse = zstd_enc::dev::zse;
+    auto launch = [&](uint8_t* slots, uint64_t slot, uint32_t* sizes, uint32_t nb, uint32_t nblocks) -> int {
+        const int grid = wave_grid(ctx, nblocks, zstd_enc::WAVES);
+        uint8_t* lits;
+        uint64_t* seqs;
+        // per wave of the grid: the literals and the sequences of one zstd block
+        BH_TRY(get_scratch(ctx, "zstd_enc_literals", (uint64_t)grid * zstd_enc::WAVES * zse::BLOCK_MAX, (void**)&lits));
+        BH_TRY(get_scratch(ctx, "zstd_enc_sequences", (uint64_t)grid * zstd_enc::WAVES * zse::MAXSEQ * 8, (void**)&seqs));
+        BH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(zstd_enc::compress_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)zstd_enc::LDS_BYTES));
+        hipLaunchKernelGGL(zstd_enc::compress_kernel, dim3(grid), dim3(64 * zstd_enc::WAVES), zstd_enc::LDS_BYTES, ctx->stream, (const uint8_t*)src,
+                           cbytes, nb, blocksize, slots, slot, sizes, nblocks, lits, seqs);
+        return BH_OK;
+    };
+    return blosc_frame::compress_frames(ctx, src, nframes, cbytes, blocksize, typesize, shuffle_mode, 4, "zstd_enc", zstd_enc::slot_bytes(blocksize), launch,
+                                        out, foff);
 }
 
 // The encoder on the host (no GPU, no context): src[0, n) -> one zstd frame in dst[0, *csize), or — when the frame would not

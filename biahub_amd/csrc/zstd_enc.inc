@@ -14,11 +14,12 @@
 // and consumer.  The wide parts run on ZS_WIDTH lanes: gathering and counting literals, ranking the symbols by count, and
 // packing the Huffman streams (a prefix sum over the code lengths of ZS_WIDTH symbols gives each its bit position; the codes
 // are OR-ed into a small bit buffer, whole words of which leave for the output).  The matcher's search loop is the one part
-// written twice: ballot-driven on the device (the structure of lz4::compress_kernel), a plain serial loop on the host.
+// written twice: ballot-driven on the device (the structure of lz4::compress_kernel, with its wave_extend), a plain serial loop
+// on the host.
 //
-// The including file defines: ZS_FN (function qualifier), ZS_CONST, ZS_LANE_DECL, ZS_SERIAL, ZS_SYNC(), ZS_WIDTH,
-// zs_scan_excl(v, &total), zs_atomic_or(p, v), zs_atomic_inc(p), zs_wait_own_stores(), zs_load_own(p); and ZSE_DEVICE for the
-// wave-wide search loop.
+// The including file brings in zstd_lanes.inc first (ZS_FN, ZS_CONST, ZS_LANE_DECL, ZS_SERIAL, ZS_SYNC(), ZS_WIDTH,
+// zs_scan_excl(v, &total), zs_atomic_or(p, v), zs_atomic_inc(p), zs_wait_own_stores(), zs_load_own(p)); its ZS_TARGET_DEVICE
+// selects the wave-wide search loop.  Limits, tables and the FSE symbol spread are the decoder's: zstd_format.inc.
 //
 // Output bound.  Block k of a frame writes only inside [op_k, op_k + 3 + bs_k): its compressed body is abandoned as soon as it
 // could reach bs_k bytes (every writer checks its position against `limit` first) and a Raw_Block is exactly 3 + bs_k bytes;
@@ -27,10 +28,8 @@
 
 namespace zse {
 
-#include "zstd_tables.inc"
+#include "zstd_format.inc"
 
-constexpr uint32_t BLOCK_MAX = 128u * 1024u;
-constexpr int HUF_MAXBITS = 11;
 constexpr int HASH_LOG = 12;
 // A candidate is four equal bytes (the hash), a match is taken from ACCEPT bytes on: a sequence costs 20 to 30 bits in the
 // predefined tables, more than the Huffman-coded literals a shorter match would replace (measured in DESIGN.md 3.4)
@@ -41,7 +40,6 @@ constexpr uint32_t MAXSEQ = BLOCK_MAX / ACCEPT + 8;
 
 constexpr uint64_t frame_bound(uint64_t n) { return 9 + 3 * ((n + BLOCK_MAX - 1) / BLOCK_MAX) + n; }
 
-enum { T_LL = 0, T_OF = 1, T_ML = 2, T_HW = 3 };
 enum { LIT_RAW = 0, LIT_RLE = 1, LIT_HUF = 2 };
 
 constexpr int FSE_MAXLOG = 8;  // the largest table this encoder builds (the format allows 9 for LL and ML)
@@ -80,13 +78,8 @@ struct Match {
     uint32_t anchor, nl, nseq, carry_len, carry_off;
 };
 
-ZS_FN inline int highbit(uint32_t v) { return 31 - __builtin_clz(v); }  // v > 0
-ZS_FN inline uint32_t ld32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-ZS_FN inline void st32(uint8_t* p, uint32_t v) { __builtin_memcpy(p, &v, 4); }
+using blosc_frame::ld32;
+using blosc_frame::st32;
 
 // forward bit writer, least significant bit first (the FSE table description and, closed by a 1 bit, the backward streams)
 struct BitW {
@@ -119,26 +112,17 @@ struct BitW {
 };
 
 // ---- FSE ----------------------------------------------------------------------------------------------------------------------
-// the symbol spread of the decoder (§4.1.1), then every symbol's positions in ascending order
+// the symbol spread of the decoder (fse_spread), then every symbol's positions in ascending order
 ZS_FN void fse_enc_build(FseEnc* E, const int16_t* norm, int nsym, int log, uint8_t* tsym, uint16_t* tnxt) {
-    const uint32_t size = 1u << log, step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    uint32_t high = size, pos = 0, run = 0;
-    for (int s = 0; s < nsym; ++s)
-        if (norm[s] == -1) tsym[--high] = (uint8_t)s;
-    for (int s = 0; s < nsym; ++s) {
-        const uint32_t cnt = norm[s] < 0 ? 1u : (uint32_t)norm[s];
+    uint32_t run = 0;
+    // (norm sums to the table size: fse_normalize, the predefined distributions)
+    fse_spread(tsym, norm, nsym, log, [&](int s, uint32_t cnt) {
         E->cum[s] = (uint16_t)run;
         E->cnt[s] = (uint16_t)cnt;
         tnxt[s] = (uint16_t)run;
         run += cnt;
-        if (norm[s] <= 0) continue;
-        for (int i = 0; i < norm[s]; ++i) {
-            tsym[pos] = (uint8_t)s;
-            do pos = (pos + step) & mask;
-            while (pos >= high);
-        }
-    }
-    for (uint32_t i = 0; i < size; ++i) E->state[tnxt[tsym[i]]++] = (uint8_t)i;
+    });
+    for (uint32_t i = 0; i < (1u << log); ++i) E->state[tnxt[tsym[i]]++] = (uint8_t)i;
     E->log = (uint32_t)log;
 }
 // states are kept as table position + table size, in [size, 2 size)
@@ -424,7 +408,8 @@ ZS_FN inline uint64_t seq_pack(uint32_t ll, uint32_t ml, uint32_t off) { return 
 // Predefined_Mode; one code only: RLE_Mode; else FSE_Compressed_Mode with a table of 2^5 to 2^FSE_MAXLOG states.
 ZS_FN uint32_t seq_table(Work* W, int t, const uint32_t* cnt, uint32_t nseq, uint8_t* out, uint32_t& pos) {
     FseEnc* E = &W->fse[t];
-    const int nmax = t == T_LL ? 36 : (t == T_OF ? 29 : 53);
+    const Predef pd = predefined(t);
+    const int nmax = pd.nsym;
     int distinct = 0, last = 0;
     for (int s = 0; s < nmax; ++s)
         if (cnt[s]) {
@@ -432,9 +417,8 @@ ZS_FN uint32_t seq_table(Work* W, int t, const uint32_t* cnt, uint32_t nseq, uin
             last = s;
         }
     if (nseq < 64) {
-        const int8_t* src = t == T_LL ? LL_NORM : (t == T_OF ? OF_NORM : ML_NORM);
-        for (int s = 0; s < nmax; ++s) W->norm[s] = src[s];
-        fse_enc_build(E, W->norm, nmax, t == T_OF ? 5 : 6, W->tsym, W->tnxt);
+        for (int s = 0; s < nmax; ++s) W->norm[s] = pd.norm[s];
+        fse_enc_build(E, W->norm, nmax, pd.log, W->tsym, W->tnxt);
         return 0;
     }
     if (distinct == 1) {  // a table of one state, no bits
@@ -573,7 +557,7 @@ ZS_FN void match_block(const uint8_t* in, uint32_t n, uint32_t start, uint32_t b
         m.carry_len = 0;
     }
     unsigned short* table = W->table;
-#ifdef ZSE_DEVICE
+#ifdef ZS_TARGET_DEVICE
     while (ip < bend && m.nseq < MAXSEQ) {  // 64 positions per step
         const uint32_t p = ip + lane;
         const bool valid = p < bend && p + 4 <= n;
@@ -597,27 +581,7 @@ ZS_FN void match_block(const uint8_t* in, uint32_t n, uint32_t start, uint32_t b
             const int first = __builtin_ctzll(mask);
             const uint32_t mp = ip + first;
             const uint32_t mc = (uint32_t)__builtin_amdgcn_readlane((int)cand, first);
-            uint32_t len = MINMATCH;
-            for (;;) {  // extend 256 bytes per step, to the end of the frame
-                const uint32_t q = mp + len + 4 * lane;
-                const bool in_range = q + 4 <= n;
-                const uint32_t a = in_range ? ld32(in + q) : 0u, c = in_range ? ld32(in + (mc + len + 4 * lane)) : 1u;
-                const uint32_t x = a ^ c;
-                const unsigned long long neq = __ballot(x != 0u || !in_range);
-                if (neq == 0ull) {
-                    len += 256;
-                    continue;
-                }
-                const int fl = __builtin_ctzll(neq);
-                len += 4 * fl;
-                if (mp + len + 4 <= n) {
-                    const uint32_t xf = (uint32_t)__builtin_amdgcn_readlane((int)x, fl);
-                    len += (uint32_t)__builtin_ctz(xf) >> 3;
-                } else {
-                    while (mp + len < n && in[mp + len] == in[mc + len]) ++len;  // at most three bytes (uniform loop)
-                }
-                break;
-            }
+            const uint32_t len = blosc_frame::wave_extend(in, mp, mc, n, (int)lane);  // to the end of the frame
             if (len < ACCEPT) {  // too short to pay for a sequence: the next candidate of the window
                 mask &= mask - 1;
                 continue;

@@ -3,8 +3,9 @@
 // The wave's control flow is uniform.  What is serial by nature — headers, FSE and Huffman table descriptions, the sequence
 // bitstream — runs on lane 0 (ZS_SERIAL) and hands its results to the other lanes through the wave's LDS record (`Lds`), always
 // with ZS_SYNC (a wavefront fence and barrier) between producer and consumer.  The wide parts — Huffman table fill, literal
-// copies, match copies — run on all lanes (ZS_LANES).  The including file defines these three macros, `ZS_CONST` for the
-// constant tables, `zs_wait_own_stores()` and `zs_load_own(p)` (a byte of this wave's own earlier global output).
+// copies, match copies — run on all ZS_WIDTH lanes.  The macros, `zs_wait_own_stores()` and `zs_load_own(p)` (a byte of this
+// wave's own earlier global output) come from zstd_lanes.inc, which the including file brings in first: for the wavefront
+// (zstd.hip's kernel) and, with one lane, for the host (bh_host_zstd_decompress: CPU tests and a host sanitizer reach the parser).
 //
 // Every bound is checked without overflow: input positions against the frame's csize, output positions against dlen, match
 // offsets against the bytes produced so far, table logs against their RFC limits, and the backward bitstreams for under- and
@@ -12,14 +13,10 @@
 
 namespace zs {
 
-constexpr int NB = 128;                    // sequences decoded per batch
-constexpr uint32_t BLOCK_MAX = 128u * 1024u;
-constexpr int HUF_MAXBITS = 11;
+#include "zstd_format.inc"
+
+constexpr int NB = 128;                      // sequences decoded per batch
 constexpr uint32_t LIT_SCRATCH = BLOCK_MAX;  // per wave: Huffman-coded literals of one block
-
-#include "zstd_tables.inc"
-
-enum { T_LL = 0, T_OF = 1, T_ML = 2 };
 constexpr int TAB_OFF[3] = {0, 512, 768};  // LL: 2^9 entries, OF: 2^8, ML: 2^9
 constexpr int TAB_MAXLOG[3] = {9, 8, 9};
 constexpr int TAB_MAXSYM[3] = {35, 31, 52};
@@ -48,15 +45,13 @@ struct Lds {
     Ctl c;
 };
 
-__device__ __forceinline__ int highbit(uint32_t v) { return 31 - __builtin_clz(v); }  // v > 0
-
 // backward bitstream (§4.1) over p[0, n): `off` bits remain below the cursor; bits below 0 read as zeros
 struct BitBack {
     const uint8_t* p;
     uint32_t n;
     int32_t off, wlo;
     uint64_t w;
-    __device__ bool init(const uint8_t* p_, uint32_t n_) {
+    ZS_FN bool init(const uint8_t* p_, uint32_t n_) {
         p = p_;
         n = n_;
         wlo = 1 << 30;
@@ -67,7 +62,7 @@ struct BitBack {
         off = (int32_t)(8 * (n - 1)) + highbit(last);
         return true;
     }
-    __device__ void reload() {
+    ZS_FN void reload() {
         int32_t bs = ((off + 7) >> 3) - 8;
         bs = bs < 0 ? 0 : bs;
         uint64_t v = 0;
@@ -80,7 +75,7 @@ struct BitBack {
         w = v;
         wlo = 8 * bs;
     }
-    __device__ uint32_t peek(int k) {  // 1 <= k <= 32: bits [off - k, off)
+    ZS_FN uint32_t peek(int k) {  // 1 <= k <= 32: bits [off - k, off)
         if (off <= 0) return 0;
         const int32_t lo = off - k;
         if (lo < wlo || off > wlo + 64) reload();
@@ -88,7 +83,7 @@ struct BitBack {
         if (lo >= wlo) return (uint32_t)((w >> (lo - wlo)) & mask);
         return (uint32_t)((w << (wlo - lo)) & mask);  // (wlo == 0: zeros below the stream)
     }
-    __device__ uint32_t read(int k) {
+    ZS_FN uint32_t read(int k) {
         if (k == 0) return 0;
         const uint32_t v = peek(k);
         off -= k;
@@ -97,7 +92,7 @@ struct BitBack {
 };
 
 // k (<= 24) bits at bit `bo` of in[0, avail), LSB first; zeros beyond
-__device__ __forceinline__ uint32_t fwd_bits(const uint8_t* in, uint32_t avail, uint32_t bo, int k) {
+ZS_FN inline uint32_t fwd_bits(const uint8_t* in, uint32_t avail, uint32_t bo, int k) {
     uint32_t v = 0;
     const uint32_t b0 = bo >> 3;
     for (int j = 0; j < 4; ++j)
@@ -106,7 +101,7 @@ __device__ __forceinline__ uint32_t fwd_bits(const uint8_t* in, uint32_t avail, 
 }
 
 // FSE table description (§4.1.1) at in[ip, lim) -> norm[0, nsym), log; advances ip
-__device__ bool fse_header(const uint8_t* in, uint32_t& ip, uint32_t lim, int maxlog, int maxsym, int16_t* norm, int& nsym, int& log) {
+ZS_FN bool fse_header(const uint8_t* in, uint32_t& ip, uint32_t lim, int maxlog, int maxsym, int16_t* norm, int& nsym, int& log) {
     if (ip >= lim) return false;
     const uint8_t* p = in + ip;
     const uint32_t avail = lim - ip;
@@ -156,28 +151,13 @@ __device__ bool fse_header(const uint8_t* in, uint32_t& ip, uint32_t lim, int ma
 }
 
 // decode table from normalized counts (§4.1.1): entries symbol | nbits << 8 | baseline << 16
-__device__ bool fse_build(uint32_t* tab, const int16_t* norm, uint16_t* sdesc, int nsym, int log) {
+ZS_FN bool fse_build(uint32_t* tab, const int16_t* norm, uint16_t* sdesc, int nsym, int log) {
     const uint32_t size = 1u << log;
-    uint32_t high = size, total = 0;
+    uint32_t total = 0;
     for (int s = 0; s < nsym; ++s) total += norm[s] < 0 ? 1u : (uint32_t)norm[s];
     if (total != size) return false;
-    for (int s = 0; s < nsym; ++s)
-        if (norm[s] == -1) {
-            tab[--high] = (uint32_t)s;
-            sdesc[s] = 1;
-        }
-    const uint32_t step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    uint32_t pos = 0;
-    for (int s = 0; s < nsym; ++s) {
-        if (norm[s] <= 0) continue;
-        sdesc[s] = (uint16_t)norm[s];
-        for (int i = 0; i < norm[s]; ++i) {
-            tab[pos] = (uint32_t)s;
-            do pos = (pos + step) & mask;
-            while (pos >= high);
-        }
-    }
-    if (pos != 0) return false;
+    // sdesc[s]: the symbol's next sub-state, from its count up
+    if (fse_spread(tab, norm, nsym, log, [&](int s, uint32_t n) { sdesc[s] = (uint16_t)n; }) < 0) return false;
     for (uint32_t i = 0; i < size; ++i) {
         const uint32_t s = tab[i] & 0xffu;
         const uint32_t d = sdesc[s]++;
@@ -188,15 +168,14 @@ __device__ bool fse_build(uint32_t* tab, const int16_t* norm, uint16_t* sdesc, i
     return true;
 }
 
-__device__ bool fse_predefined(Lds* L, int t) {
-    const int8_t* src = t == T_LL ? LL_NORM : (t == T_OF ? OF_NORM : ML_NORM);
-    const int nsym = t == T_LL ? 36 : (t == T_OF ? 29 : 53);
-    for (int s = 0; s < nsym; ++s) L->norm[s] = src[s];
-    return fse_build(L->tab + TAB_OFF[t], L->norm, L->sdesc, nsym, t == T_OF ? 5 : 6);
+ZS_FN bool fse_predefined(Lds* L, int t) {
+    const Predef p = predefined(t);
+    for (int s = 0; s < p.nsym; ++s) L->norm[s] = p.norm[s];
+    return fse_build(L->tab + TAB_OFF[t], L->norm, L->sdesc, p.nsym, p.log);
 }
 
 // Huffman tree description (§4.2.1) at in[ip, lim): weights -> L->hw, per-symbol table starts -> L->hstart
-__device__ bool huf_header(const uint8_t* in, uint32_t& ip, uint32_t lim, Lds* L, Ctl* c) {
+ZS_FN bool huf_header(const uint8_t* in, uint32_t& ip, uint32_t lim, Lds* L, Ctl* c) {
     if (ip >= lim) return false;
     const uint32_t hdr = in[ip++];
     uint32_t nw = 0;
@@ -273,7 +252,7 @@ __device__ bool huf_header(const uint8_t* in, uint32_t& ip, uint32_t lim, Lds* L
 #include "zstd_block.inc"
 
 // One frame: in[0, cs) -> out[0, n).  `lit`: this wave's LIT_SCRATCH bytes of global scratch.  Returns false on a corrupt frame.
-__device__ bool decode_frame(const uint8_t* __restrict__ in, uint32_t cs, uint8_t* __restrict__ out, uint32_t n, uint8_t* __restrict__ lit,
+ZS_FN bool decode_frame(const uint8_t* __restrict__ in, uint32_t cs, uint8_t* __restrict__ out, uint32_t n, uint8_t* __restrict__ lit,
                              Lds* L) {
     ZS_LANE_DECL;
     Ctl* c = &L->c;
@@ -351,12 +330,10 @@ __device__ bool decode_frame(const uint8_t* __restrict__ in, uint32_t cs, uint8_
         const uint32_t btype = c->btype;
         if (btype == 0 || btype == 1) {
             const uint32_t op = c->op, len = c->len, rle = c->rle, src = c->src;
-            ZS_LANES {
-                if (btype == 0)
-                    for (uint32_t j = lane; j < len; j += 64) out[op + j] = in[src + j];
-                else
-                    for (uint32_t j = lane; j < len; j += 64) out[op + j] = (uint8_t)rle;
-            }
+            if (btype == 0)
+                for (uint32_t j = lane; j < len; j += ZS_WIDTH) out[op + j] = in[src + j];
+            else
+                for (uint32_t j = lane; j < len; j += ZS_WIDTH) out[op + j] = (uint8_t)rle;
             ZS_SYNC();
             ZS_SERIAL { c->op = op + len; }
         } else {

@@ -266,6 +266,11 @@ int bh_blosc_zstd_compress(bh_ctx* ctx, const void* src, uint32_t nframes, uint3
  * dst[0, *csize), or, when the frame would not be smaller than n, the n bytes themselves (*csize == n: the container's mark
  * for a stored block).  1 <= n <= 2^30, cap >= n. */
 int bh_host_zstd_compress(const void* src, uint64_t n, void* dst, uint64_t cap, uint64_t* csize);
+/* The host form of the zstd decoder behind bh_zstd_decompress_streams (no GPU, no context; the same source compiled with one
+ * lane), for one stream under that entry's per-stream contract: csize == n marks a stored stream, which is copied; otherwise
+ * src[0, csize) is one complete zstd frame whose output must be exactly the n bytes of dst.  BH_ERR_INVALID on a corrupt
+ * frame.  csize, n < 2^31.  It exists to test and debug the decoder; no reader uses it. */
+int bh_host_zstd_decompress(const void* src, uint64_t csize, void* dst, uint64_t n);
 /* LZ4 streams back to bytes on the device: stream i is csize[i] bytes at src + soff[i] and decodes to dlen[i] bytes at
  * dst + doff[i] (device arrays of nstreams entries; csize == dlen marks a stored stream).  The caller reads the Blosc frame's
  * block table on the host — a block is one stream, or `typesize` streams when its writer split it (c-blosc 1.21 splits lz4

@@ -91,26 +91,8 @@ def _expect_corrupt(frames, gpu, index):
 
 @pytest.mark.gpu
 def test_zstd_device_reports_corrupt_frames(gpu):
-    good = zstd_corpus.raw_frames()
-    camera = [f for f in good if (b"\x28\xb5\x2f\xfd" == f[0][:4])][:4]
-    frame, want = camera[1]
-    # a one-block frame with 4-stream Huffman literals
-    huf = next(fw for fw in good if len(fw[1]) == 32768 and ("literals", "huf4") in zstd_corpus.walk(fw[0]))
-    did = 5 + (0 if (frame[4] >> 5) & 1 else 1)  # the dictionary ID field follows the window descriptor
-    cases = {
-        "truncated": (frame[: len(frame) // 2], want),
-        "dictionary": (frame[:4] + bytes([frame[4] | 1]) + frame[5:did] + b"\x07" + frame[did:], want),
-        "content_size": (frame, want + b"\0"),
-        "offset": zstd_corpus.hand_frames()["offset_past_output"][0:1] + (bytes(7),),
-    }
-    # damaged Huffman tree description: the weights header byte of the first compressed block -> 255 weights of 15
-    hb = bytearray(huf[0])
-    fhd = hb[4]
-    ip = 5 + (0 if (fhd >> 5) & 1 else 1) + ((1 if (fhd >> 5) & 1 else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6))
-    sf = (hb[ip + 3] >> 2) & 3
-    q = ip + 3 + (3, 3, 4, 5)[sf]
-    hb[q:q + 64] = b"\xff" * 64
-    cases["huffman_header"] = (bytes(hb), huf[1])
+    camera, cases = zstd_corpus.corrupt_cases()
+    assert set(cases) == {"truncated", "dictionary", "content_size", "offset", "huffman_header"}
     for bad in cases.values():
         _expect_corrupt([camera[0], bad, camera[2]], gpu, 1)
     # a good decode afterwards in the same process

@@ -1,7 +1,9 @@
 """csrc/zstd_enc.hip on the GPU: Blosc frames with zstd inside, made on the device.  The judge of every zstd frame is pyarrow's
 libzstd (``codecs.zstd_decompress``); the project's own decoders and, where the image has it, the real c-blosc read them too."""
 import ctypes
+import json
 import os
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -50,18 +52,10 @@ def _check_streams(frame: bytes, permuted: np.ndarray) -> list:
 def test_zstd_device_compressor_frames(gpu, dtype, mode):
     """Permute -> zstd frames -> packed Blosc frames, all on the GPU: four chunks with a short last block, read back by libzstd
     stream by stream, by the host decoder, by the device decoder in one launch and by the real c-blosc."""
-    rng = np.random.default_rng(12)
     ts = np.dtype(dtype).itemsize
-    n_el = 190_000  # per chunk: 190 / 380 / 760 KB -> one to three 256-KiB blocks, the last one short
-    x = np.arange(n_el)
-    chunks = [
-        (300 + 200 * np.sin(x / 37.0) + rng.poisson(2, n_el)).astype(dtype),     # camera-like: compressible
-        rng.integers(0, 256, n_el * ts, dtype=np.uint8).view(dtype),                # noise in every bit: incompressible
-        np.zeros(n_el, dtype),                                                      # one long run
-        np.where(x % 5000 < 4000, 1234, x % 251).astype(dtype),                     # runs and ramps
-    ]
+    chunks = zstd_corpus.compressor_chunks(dtype)  # 190 / 380 / 760 KB each: one to three 256-KiB blocks, the last one short
     raw = np.concatenate([c.view(np.uint8) for c in chunks])
-    cbytes = n_el * ts
+    cbytes = chunks[0].nbytes
     bsz = codecs.default_blocksize(ts)
     src = torch.from_numpy(raw).to(gpu)
     filt = torch.empty_like(src)
@@ -99,6 +93,17 @@ def test_zstd_device_compressor_frames(gpu, dtype, mode):
     assert cbytes + 16 + 4 * nb <= sizes[1] <= cbytes + 16 + 8 * nb, sizes  # noise: every block stored
     assert all(s <= cbytes + 16 + 8 * nb for s in sizes), sizes               # no frame larger than stored
     assert sizes[2] < 0.001 * cbytes, sizes                                    # zeros: a few sequences per block
+
+
+@pytest.mark.gpu
+def test_zstd_device_encoder_bytes_are_pinned(gpu):
+    """The device encoder resets its hash table per frame and its atomics only count, so its frames are a function of the input
+    alone: the four cases of ``test_zstd_device_compressor_frames`` and a chunk of two 256-KiB blocks and a third of 1000 bytes,
+    byte for byte against digests recorded on an MI355X before the encoder's source was last rearranged (the fixture names the
+    commit).  A deliberate change to the encoder re-records the fixture."""
+    assert [tuple(c) for c in zstd_corpus.DEVICE_DIGEST_CASES] == [("u2", 2), ("f4", 2), ("u2", 1), ("u1", 0)]
+    pinned = json.loads((Path(__file__).parent / "golden" / "zstd_enc_device_digests.json").read_text())["digests"]
+    assert zstd_corpus.device_encoder_digests(gpu) == pinned
 
 
 @pytest.mark.gpu

@@ -3,6 +3,9 @@ compiled with one lane).  The judge is pyarrow's libzstd (``codecs.zstd_decompre
 the encoder writes must decode there to the input, bit for bit; ``zstd_corpus.walk`` and a reading of the first block's
 headers prove which parts of RFC 8878 the inputs reach."""
 import ctypes
+import hashlib
+import json
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -10,8 +13,7 @@ import pytest
 import zstd_corpus
 from biahub_amd import _lib, codecs
 
-EDGE_SIZES = (1, 2, 3, 4, 12, 13, 127, 131071, 131072, 131073, 262143)  # 131073: a second zstd block of one byte
-TYPESIZE = dict(camera=2, float8=4, ramp=2, sparse=2, constant=2, alpha4=1, tile4=1, runs=1, zeros_tail=1)
+TYPESIZE = zstd_corpus.TYPESIZE
 
 
 def _rng():
@@ -73,21 +75,17 @@ def _first_block(frame: bytes) -> dict:
 @pytest.fixture(scope="module")
 def corpus_frames():
     """name -> (input, frame) for every data kind at both block sizes, raw and as the store permutes it, plus the edge sizes."""
-    out = {}
-    for nbytes in zstd_corpus.BLOCKS:
-        for kind, data in zstd_corpus.data_kinds(nbytes).items():
-            out[f"{kind}/{nbytes}"] = (data, _encode(data))
-            if TYPESIZE[kind] > 1:
-                p = _permuted(kind, data)
-                out[f"{kind}/{nbytes}/permuted"] = (p, _encode(p))
-    cam = zstd_corpus.data_kinds()["camera"]
-    for n in EDGE_SIZES:
-        out[f"camera[:{n}]"] = (cam[:n], _encode(cam[:n]))
-    rng = _rng()
-    # a block of noise (Raw_Block) in front of a block of zeros (Compressed_Block): the frame shrinks, the first block cannot
-    mixed = np.concatenate([rng.integers(0, 256, 131072).astype(np.uint8), np.zeros(131072, np.uint8)])
-    out["noise+zeros"] = (mixed, _encode(mixed))
-    return out
+    return {name: (data, _encode(data)) for name, data in zstd_corpus.encoder_inputs().items()}
+
+
+def test_encoder_bytes_are_pinned(corpus_frames):
+    """What the host encoder writes, byte for byte, against digests recorded before the encoder's source was last rearranged
+    (the fixture names the commit): a refactor changes no byte.  A deliberate change to the encoder re-records the fixture."""
+    pinned = json.loads((Path(__file__).parent / "golden" / "zstd_enc_host_digests.json").read_text())["digests"]
+    got = {name: hashlib.sha256(f).hexdigest() for name, (_, f) in corpus_frames.items()}
+    got.update({name: hashlib.sha256(_encode(d)).hexdigest() for name, d in zstd_corpus.edge_inputs().items()})
+    assert got.keys() == pinned.keys()
+    assert [k for k in got if got[k] != pinned[k]] == []
 
 
 def test_corpus_round_trips_through_libzstd(corpus_frames):

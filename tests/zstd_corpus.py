@@ -42,6 +42,121 @@ def raw_frames():
     return out
 
 
+TYPESIZE = dict(camera=2, float8=4, ramp=2, sparse=2, constant=2, alpha4=1, tile4=1, runs=1, zeros_tail=1)
+ENCODER_EDGE_SIZES = (1, 2, 3, 4, 12, 13, 127, 131071, 131072, 131073, 262143)  # 131073: a second zstd block of one byte
+# frame header forms (content size in 1, 2 and 4 bytes: below 256, below 65792, above) and the 128-KiB zstd block edge
+EDGE_LENGTHS = (1, 2, 3, 255, 256, 65791, 65792, 131071, 131072, 131073)
+
+
+def encoder_inputs() -> dict:
+    """name -> uint8 input of the host encoder's tests: every data kind at both block sizes, raw and as the store permutes it
+    (bit-shuffled for typesize 2 and 4), camera prefixes of the edge sizes, and a block of noise in front of a block of zeros."""
+    from biahub_amd import codecs
+
+    out = {}
+    for nbytes in BLOCKS:
+        for kind, data in data_kinds(nbytes).items():
+            out[f"{kind}/{nbytes}"] = data
+            if TYPESIZE[kind] > 1:
+                out[f"{kind}/{nbytes}/permuted"] = codecs.filter_host(data, 262144, TYPESIZE[kind], codecs.BLOSC_BITSHUFFLE)
+    cam = data_kinds()["camera"]
+    for n in ENCODER_EDGE_SIZES:
+        out[f"camera[:{n}]"] = cam[:n]
+    rng = np.random.default_rng(11)
+    # a block of noise (Raw_Block) in front of a block of zeros (Compressed_Block): the frame shrinks, the first block cannot
+    out["noise+zeros"] = np.concatenate([rng.integers(0, 256, 131072).astype(np.uint8), np.zeros(131072, np.uint8)])
+    return out
+
+
+def edge_inputs() -> dict:
+    """name -> uint8 input at the lengths where the frame encoder takes another path (``EDGE_LENGTHS``), and 256 KiB + 3 bytes
+    with one long run from byte 100000 to byte 200000: the match that covers it is cut at the 128-KiB block edge and its
+    remainder carried into the next block."""
+    cam = data_kinds(524288)["camera"]
+    out = {f"edge/{n}": cam[:n] for n in EDGE_LENGTHS}
+    carry = cam[:262144 + 3].copy()
+    carry[100000:200000] = 0x5a
+    out["edge/262147_run_over_block_edge"] = carry
+    return out
+
+
+def corrupt_cases():
+    """(camera, cases): four good frames, and name -> (frame, expected bytes) of frames every decoder must refuse."""
+    good = raw_frames()
+    camera = [f for f in good if (b"\x28\xb5\x2f\xfd" == f[0][:4])][:4]
+    frame, want = camera[1]
+    # a one-block frame with 4-stream Huffman literals
+    huf = next(fw for fw in good if len(fw[1]) == 32768 and ("literals", "huf4") in walk(fw[0]))
+    did = 5 + (0 if (frame[4] >> 5) & 1 else 1)  # the dictionary ID field follows the window descriptor
+    cases = {
+        "truncated": (frame[: len(frame) // 2], want),
+        "dictionary": (frame[:4] + bytes([frame[4] | 1]) + frame[5:did] + b"\x07" + frame[did:], want),
+        "content_size": (frame, want + b"\0"),
+        "offset": hand_frames()["offset_past_output"][0:1] + (bytes(7),),
+    }
+    # damaged Huffman tree description: the weights header byte of the first compressed block -> 255 weights of 15
+    hb = bytearray(huf[0])
+    fhd = hb[4]
+    ip = 5 + (0 if (fhd >> 5) & 1 else 1) + ((1 if (fhd >> 5) & 1 else 0) if fhd >> 6 == 0 else 1 << (fhd >> 6))
+    sf = (hb[ip + 3] >> 2) & 3
+    q = ip + 3 + (3, 3, 4, 5)[sf]
+    hb[q:q + 64] = b"\xff" * 64
+    cases["huffman_header"] = (bytes(hb), huf[1])
+    return camera, cases
+
+
+def compressor_chunks(dtype: str) -> list:
+    """Four chunks of 190000 elements for the device writers: camera-like, noise, zeros, runs and ramps."""
+    rng = np.random.default_rng(12)
+    ts = np.dtype(dtype).itemsize
+    n_el = 190_000  # per chunk: 190 / 380 / 760 KB -> one to three 256-KiB blocks, the last one short
+    x = np.arange(n_el)
+    return [
+        (300 + 200 * np.sin(x / 37.0) + rng.poisson(2, n_el)).astype(dtype),     # camera-like: compressible
+        rng.integers(0, 256, n_el * ts, dtype=np.uint8).view(dtype),                # noise in every bit: incompressible
+        np.zeros(n_el, dtype),                                                      # one long run
+        np.where(x % 5000 < 4000, 1234, x % 251).astype(dtype),                     # runs and ramps
+    ]
+
+
+DEVICE_DIGEST_CASES = (("u2", 2), ("f4", 2), ("u2", 1), ("u1", 0))
+
+
+def device_encoder_digests(gpu) -> dict:
+    """name -> SHA-256 of the Blosc frames (each ``header.cbytes`` long, back to back, without the alignment gaps between them)
+    that ``codecs.blosc_zstd_compress_device`` makes of the four ``compressor_chunks`` cases and of one chunk of two 256-KiB
+    blocks and a third of 1000 bytes."""
+    import hashlib
+
+    import torch
+
+    from biahub_amd import codecs
+
+    def digest(filt, nframes, cbytes, bsz, ts, mode):
+        packed, offs = codecs.blosc_zstd_compress_device(filt, nframes, cbytes, bsz, ts, mode)
+        host = packed[: offs[-1]].cpu().numpy()
+        h = hashlib.sha256()
+        for i in range(nframes):
+            n = int.from_bytes(host[offs[i] + 12: offs[i] + 16].tobytes(), "little")  # the header's cbytes
+            assert offs[i] + n <= offs[i + 1]
+            h.update(host[offs[i]: offs[i] + n].tobytes())
+        return h.hexdigest()
+
+    out = {}
+    for dtype, mode in DEVICE_DIGEST_CASES:
+        chunks = compressor_chunks(dtype)
+        ts, cbytes = np.dtype(dtype).itemsize, chunks[0].nbytes
+        bsz = codecs.default_blocksize(ts)
+        src = torch.from_numpy(np.concatenate([c.view(np.uint8) for c in chunks])).to(gpu)
+        filt = torch.empty_like(src)
+        for i in range(len(chunks)):
+            codecs.filter_device(src[i * cbytes:(i + 1) * cbytes], filt[i * cbytes:(i + 1) * cbytes], bsz, ts, mode)
+        out[f"{dtype}/mode{mode}"] = digest(filt, len(chunks), cbytes, bsz, ts, mode)
+    three = data_kinds(1 << 20)["camera"][: 2 * 262144 + 1000]  # the per-block stride and the short last block
+    out["camera/2x256KiB+1000"] = digest(torch.from_numpy(three).to(gpu), 1, three.size, 262144, 1, 0)
+    return out
+
+
 def walk(frame: bytes) -> set:
     """The RFC 8878 features a zstd frame uses: ("block", raw|rle|compressed), ("literals", raw|rle|huf1|huf4|treeless) and
     ("seq", LL|OF|ML, predefined|rle|fse|repeat)."""
