@@ -52,6 +52,9 @@ SIGNATURES = {
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i64, C.POINTER(_i64)]),
     "bh_stitch_edge_shifts": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int32), _int, _i64, _i64, _i64, _int, _int,
                                      C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_vp), C.POINTER(_vp)]),
+    "bh_focus_band_table": (_int, [_i64, _i64, _f64, _f64, _f64, _f64, _f64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_i64)]),
+    "bh_focus_band_power": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _int, C.POINTER(_f64),
+                                   C.POINTER(_f64)]),
     "bh_valid_mask": (_int, [_vp, _vp, _int, _i64, _vp, C.POINTER(C.c_uint64)]),
     "bh_bits_and": (_int, [_vp, _vp, _vp, _i64]),
     "bh_bits_unpack": (_int, [_vp, _vp, _i64, _vp]),

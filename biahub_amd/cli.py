@@ -18,7 +18,7 @@ import numpy as np
 from . import parallel
 from .io import create_empty_plate, open_ome_zarr, process_single_position
 from .settings import (DeconvolveSettings, DeskewSettings, EstimateRegistrationSettings,
-                       EstimateStabilizationSettings, FlatFieldCorrectionSettings, PhaseCrossCorrSettings,
+                       EstimateStabilizationSettings, FlatFieldCorrectionSettings, FocusFindingSettings, PhaseCrossCorrSettings,
                        ProcessingImportFuncSettings, PsfFromBeadsSettings, RegistrationSettings, RichardsonLucySettings,
                        StabilizationSettings, StitchSettings)
 from .utils.cluster import echo_resources, estimate_resources, get_submitit_cluster
@@ -687,16 +687,23 @@ def optimize_registration_cli(source_position_dirpaths, target_position_dirpaths
 @click.option("--local", "-l", is_flag=True, default=False)
 def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_filepath, sbatch_filepath, local):
     """Estimate per-timepoint stabilization transforms (reference: ``biahub estimate-stabilization``,
-    estimate_stabilization.py:1223-1640).  ``stabilization_type: xyz`` with ``stabilization_method: phase-cross-corr``
-    runs here (GPU phase cross-correlation); one ``xyz_stabilization_settings/<fov>.yml`` per position feeds ``stabilize``."""
-    from .estimate_stabilization import estimate_xyz_stabilization_pcc, save_transforms
+    estimate_stabilization.py:1223-1640).  Two combinations run here: ``stabilization_type: xyz`` with ``stabilization_method:
+    phase-cross-corr`` (GPU phase cross-correlation; ``xyz_stabilization_settings/<fov>.yml``) and ``stabilization_type: z`` with
+    the reference's default ``focus-finding`` (GPU mid-band power; ``z_stabilization_settings/<fov>.yml``, or ``average.yml``
+    with ``average_across_wells``).  Each file feeds ``stabilize``."""
+    from .estimate_stabilization import estimate_xyz_stabilization_pcc, estimate_z_stabilization, save_transforms
 
     settings = yaml_to_model(config_filepath, EstimateStabilizationSettings)
     click.echo(f"Settings: {settings}")
-    if not (settings.stabilization_type == "xyz" and settings.stabilization_method == "phase-cross-corr"):
+    combo = (settings.stabilization_type, settings.stabilization_method)
+    if settings.stabilization_method == "focus-finding" and settings.stabilization_type in ("xy", "xyz"):
+        raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method 'focus-finding' registers xy with "
+                               "StackReg (pystackreg), which is not available in biahub_amd; 'focus-finding' runs here with "
+                               "stabilization_type 'z', and 'xyz' with 'phase-cross-corr'.")
+    if combo not in (("xyz", "phase-cross-corr"), ("z", "focus-finding")):
         raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method "
                                f"{settings.stabilization_method!r} is not available in biahub_amd (only 'xyz' with "
-                               "'phase-cross-corr'); use the reference biahub package for focus finding and beads.")
+                               "'phase-cross-corr' and 'z' with 'focus-finding'); use the reference biahub package for beads.")
     if settings.eval_transform_settings:
         raise click.UsageError("eval_transform_settings (transform validation / interpolation) is not available in biahub_amd")
     output_dirpath = Path(output_dirpath)
@@ -704,10 +711,25 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
     with open_ome_zarr(input_position_dirpaths[0]) as ds:
         channel_index = ds.channel_names.index(settings.stabilization_estimation_channel)
         voxel_size = list(ds.scale)
-    click.echo("Estimating xyz stabilization parameters with phase cross correlation")
-    pcc = settings.phase_cross_corr_settings or PhaseCrossCorrSettings()
-    fov_transforms = estimate_xyz_stabilization_pcc(input_position_dirpaths, output_dirpath, pcc, channel_index=channel_index,
-                                                    sbatch_filepath=sbatch_filepath, cluster="local", verbose=settings.verbose)
+        fov_yx = tuple(int(n) for n in ds.data.shape[-2:])
+    if combo == ("z", "focus-finding"):
+        from .estimate_stabilization import centre_window
+
+        focus_settings = FocusFindingSettings(**(settings.focus_finding_settings or {}))
+        try:
+            centre_window(*fov_yx, focus_settings.center_crop_xy)
+        except ValueError as e:
+            raise click.UsageError(str(e)) from None
+    if combo == ("xyz", "phase-cross-corr"):
+        click.echo("Estimating xyz stabilization parameters with phase cross correlation")
+        pcc = settings.phase_cross_corr_settings or PhaseCrossCorrSettings()
+        fov_transforms = estimate_xyz_stabilization_pcc(input_position_dirpaths, output_dirpath, pcc, channel_index=channel_index,
+                                                        sbatch_filepath=sbatch_filepath, cluster="local", verbose=settings.verbose)
+    else:
+        click.echo("Estimating z stabilization parameters with focus finding")
+        fov_transforms = estimate_z_stabilization(input_position_dirpaths, output_dirpath, focus_settings,
+                                                  channel_index=channel_index, sbatch_filepath=sbatch_filepath, cluster="local",
+                                                  verbose=settings.verbose)
     if parallel.world_info()[0] == 0:
         for fov, transforms in fov_transforms.items():
             model = StabilizationSettings(stabilization_type=settings.stabilization_type,
@@ -716,7 +738,7 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
                                           stabilization_channels=settings.stabilization_channels,
                                           affine_transform_zyx_list=[np.eye(4).tolist()], time_indices="all",
                                           output_voxel_size=voxel_size)
-            save_transforms(model, transforms, output_dirpath / "xyz_stabilization_settings" / f"{fov}.yml")
+            save_transforms(model, transforms, output_dirpath / f"{settings.stabilization_type}_stabilization_settings" / f"{fov}.yml")
     click.echo(f"Stabilization settings saved to {output_dirpath.resolve()}")
 
 

@@ -1,11 +1,16 @@
-"""Phase cross-correlation on MI355X — mirror of ``biahub/estimate_stabilization.py:199-256``.
+"""The stabilisation estimate on MI355X — mirror of ``biahub/estimate_stabilization.py``.
 
-The FFT kernel of the stabilisation *estimate*  is ``bh_phase_cross_corr``: two R2C transforms,
-the fused normalised conjugate product, C2R, |.| + first-occurrence argmax on device.  Around it this module keeps the
-reference's phase-cross-correlation call chain (``phase_cross_corr_padding``, ``get_tform_from_pcc``,
-``estimate_xyz_stabilization_pcc[_per_position]``: estimate_stabilization.py:129-196, 259-310, 444-693) so that
-``estimate-stabilization`` with ``stabilization_method: phase-cross-corr`` produces the settings ``stabilize`` consumes;
-focus finding, StackReg and bead matching are not part of this package.
+Two of the reference's methods run here, each around one device primitive:
+
+* ``phase-cross-corr`` (``stabilization_type: xyz``; :129-310, :444-693): ``bh_phase_cross_corr`` — two R2C transforms, the
+  fused normalised conjugate product, C2R, |.| + first-occurrence argmax on device — under the
+  reference's call chain ``phase_cross_corr_padding``, ``get_tform_from_pcc``, ``estimate_xyz_stabilization_pcc[_per_position]``.
+* ``focus-finding`` (``stabilization_type: z``, the reference's default method; :900-1220): ``bh_focus_band_power`` — the
+  mid-band power of every z-slice of the centre window (``biahub_amd/focus.py``) — under
+  ``estimate_z_focus_per_position``, ``get_mean_z_positions`` and ``estimate_z_stabilization``.
+
+Either way ``estimate-stabilization`` writes the per-timepoint 4x4 matrices ``stabilize`` consumes.  StackReg (xy) and bead
+matching are not part of this package.
 """
 
 from __future__ import annotations
@@ -279,6 +284,198 @@ def estimate_xyz_stabilization_pcc(input_position_dirpaths, output_folder_path, 
     if rank == 0:
         shutil.rmtree(transforms_out)
     return fov_transforms
+
+
+# ----------------------------------------------------------------------------- focus finding: the z chain (:900-1220)
+NA_DET = 1.35
+LAMBDA_ILL = 0.5
+FOCUS_CSV_COLUMNS = ("position", "time_idx", "channel", "focus_idx")
+
+
+def _write_focus_csv(path, rows) -> None:
+    import csv
+
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(FOCUS_CSV_COLUMNS)
+        w.writerows(rows)
+
+
+def _read_focus_csv(path) -> list[tuple]:
+    """Rows ``(position, time_idx int, channel, focus_idx)``; ``focus_idx`` is an int where the file holds one, a float (NaN
+    for an empty field) otherwise."""
+    import csv
+
+    def num(x):
+        if x == "":
+            return float("nan")
+        try:
+            return int(x)
+        except ValueError:
+            return float(x)
+
+    with open(path, newline="") as f:
+        return [(r["position"], int(r["time_idx"]), r["channel"], num(r["focus_idx"])) for r in csv.DictReader(f)]
+
+
+def z_transforms_from_focus(focus_idx) -> np.ndarray:
+    """``estimate_stabilization.py:980-993``: ``[eye] + [eye with [0, 3] = f - f_ref for f in focus_idx[1:]]``, ``f_ref`` the
+    first index that is neither 0 (an empty FOV, a failed estimate) nor NaN."""
+    z_ref = next((v for v in focus_idx if v != 0 and not np.isnan(v)), None)
+    if z_ref is None:
+        raise ValueError("Z index of focus reference is None, focus_idx contains only zeros")
+    out = [np.eye(4)]
+    for v in list(focus_idx)[1:]:
+        shift = np.eye(4)
+        shift[0, 3] = v - z_ref
+        out.append(shift)
+    return np.array(out)
+
+
+def merge_focus_rows(new_rows, old_rows=()) -> list[tuple]:
+    """``estimate_stabilization.py:1160-1168``: new rows first, an existing file's rows after them, duplicates on
+    ``(position, time_idx)`` dropped keeping the first, sorted by ``(position, time_idx)`` (stable)."""
+    seen, merged = set(), []
+    for r in list(new_rows) + list(old_rows):
+        key = (r[0], r[1])
+        if key not in seen:
+            seen.add(key)
+            merged.append(tuple(r))
+    return sorted(merged, key=lambda r: (r[0], r[1]))
+
+
+def centre_window(Y: int, X: int, center_crop_xy) -> tuple[slice, slice]:
+    """The reference's window ``[Y//2 - cy//2 : Y//2 + cy//2, X//2 - cx//2 : X//2 + cx//2]`` for ``center_crop_xy = [cx, cy]``
+    (:938-942).  A crop larger than the FOV is refused: the reference's slice then starts at a negative index, which numpy
+    counts from the end, and the window it cuts is off-centre (or the whole FOV, once the crop is twice the FOV)."""
+    cx, cy = (int(v) for v in center_crop_xy)
+    if cx < 2 or cy < 2 or cx > X or cy > Y:
+        raise ValueError(f"center_crop_xy {[cx, cy]} does not fit the FOV (Y, X) = ({Y}, {X}): the reference's slice would wrap to "
+                         "an off-centre window, which is not available in biahub_amd; set focus_finding_settings.center_crop_xy "
+                         "to at most the FOV")
+    return slice(Y // 2 - cy // 2, Y // 2 + cy // 2), slice(X // 2 - cx // 2, X // 2 + cx // 2)
+
+
+def estimate_z_focus_per_position(input_position_dirpath, input_channel_indices, center_crop_xy, output_path_focus_csv,
+                                  output_path_transform, verbose: bool = False, device="cuda") -> None:
+    """``estimate_stabilization.py:900-1000``: the focus slice of every (timepoint, channel) from the centre window
+    (``centre_window``); only the window is uploaded.
+    An empty window (sum 0) gets index 0.  Writes ``<row>_<col>_<fov>.csv`` and the z-shift matrices ``<row>_<col>_<fov>.npy``."""
+    import itertools
+    from pathlib import Path
+
+    from .focus import focus_from_power, midband_power_and_sum
+    from .io import open_ome_zarr
+
+    input_position_dirpath = Path(input_position_dirpath)
+    position = str(Path(*input_position_dirpath.parts[-3:]))
+    rows = []
+    with open_ome_zarr(input_position_dirpath) as dataset:
+        channel_names = dataset.channel_names
+        T, _, Z, Y, X = dataset.data.shape
+        pixel_size = float(dataset.scale[-1])
+        ys, xs = centre_window(Y, X, center_crop_xy)
+        for t, c in itertools.product(range(T), input_channel_indices):
+            window = np.asarray(dataset.data[t, c][:, ys, xs])
+            if Z == 1:
+                z_idx = 0
+            else:
+                power, total = midband_power_and_sum(window, NA_DET, LAMBDA_ILL, pixel_size, device=device)
+                if total == 0:  # an empty FOV: the focal plane is 0
+                    z_idx = 0
+                else:
+                    z_idx = focus_from_power(power)
+                    print(f"Estimating focus for timepoint {t} and channel {c}: {z_idx}")
+            rows.append((position, t, channel_names[c], z_idx))
+    output_path_focus_csv = Path(output_path_focus_csv)
+    output_path_focus_csv.mkdir(parents=True, exist_ok=True)
+    if verbose:
+        print(f"Saving focus finding results to {output_path_focus_csv}")
+    name = position.replace("/", "_")
+    _write_focus_csv(output_path_focus_csv / f"{name}.csv", rows)
+    transform = z_transforms_from_focus([r[3] for r in rows])
+    output_path_transform = Path(output_path_transform)
+    output_path_transform.mkdir(parents=True, exist_ok=True)
+    np.save(output_path_transform / f"{name}.npy", transform)
+    if verbose:
+        print(f"Saved Z transform matrices to {output_path_transform}")
+
+
+def get_mean_z_positions(dataframe_path, verbose: bool = False, method: str = "mean") -> np.ndarray:
+    """``estimate_stabilization.py:1003-1049`` without the plot: rows sorted by ``time_idx``, a focus index of 0 read as NaN,
+    then the NaN-skipping mean or median of every ``time_idx`` (NaN where a timepoint has no estimate)."""
+    if method not in ("mean", "median"):
+        raise ValueError(f"unknown method {method!r}")
+    rows = sorted(_read_focus_csv(dataframe_path), key=lambda r: r[1])
+    groups: dict = {}
+    for _, t, _, f in rows:
+        groups.setdefault(t, []).append(np.nan if f == 0 else float(f))
+    out = []
+    for t in sorted(groups):
+        v = np.array([x for x in groups[t] if not np.isnan(x)], dtype=np.float64)
+        out.append(np.nan if v.size == 0 else float(np.mean(v) if method == "mean" else np.median(v)))
+    return np.array(out, dtype=np.float64)
+
+
+def estimate_z_stabilization(input_position_dirpaths, output_folder_path, focus_finding_settings, channel_index: int,
+                             sbatch_filepath=None, cluster: str = "local", verbose: bool = False, estimate_z_index: bool = False,
+                             device="cuda"):
+    """``estimate_stabilization.py:1052-1220``: every position (sharded over ranks instead of submitit jobs); rank 0 merges
+    the per-position tables into ``positions_focus.csv`` and every rank returns ``{"average": transforms}`` with
+    ``average_across_wells``, else ``{<row>_<col>_<fov>: transforms}``; ``None`` with ``estimate_z_index``.
+    ``focus_finding_settings``: a ``FocusFindingSettings``, a dict of its fields, or ``None`` for the defaults."""
+    import shutil
+    from pathlib import Path
+
+    from . import parallel
+    from .settings import FocusFindingSettings
+
+    s = focus_finding_settings
+    if s is None:
+        s = FocusFindingSettings()
+    elif isinstance(s, dict):
+        s = FocusFindingSettings(**s)
+    input_position_dirpaths = remove_beads_fov_from_path_list(list(input_position_dirpaths), s.skip_beads_fov)
+    output_folder_path = Path(output_folder_path)
+    focus_out = output_folder_path / "z_focus_positions"
+    transforms_out = output_folder_path / "z_transforms"
+    focus_out.mkdir(parents=True, exist_ok=True)
+    transforms_out.mkdir(parents=True, exist_ok=True)
+    rank, world = parallel.init()  # binds this rank to GPU LOCAL_RANK before any device call
+    for p in parallel.shard_positions(input_position_dirpaths, rank, world):
+        estimate_z_focus_per_position(p, (channel_index,), s.center_crop_xy, focus_out, transforms_out, verbose=verbose, device=device)
+    parallel.barrier()
+    merged_path = output_folder_path / "positions_focus.csv"
+    if rank == 0:
+        csvs = sorted(focus_out.glob("*.csv"))
+        if len(csvs) != len(input_position_dirpaths):
+            print(f"Warning: {len(csvs)} focus CSV files found for {len(input_position_dirpaths)} input data paths.")
+        new_rows = [r for f in csvs for r in _read_focus_csv(f)]
+        old_rows = []
+        if merged_path.exists():
+            print("Using existing focus CSV file.")
+            old_rows = _read_focus_csv(merged_path)
+        _write_focus_csv(merged_path, merge_focus_rows(new_rows, old_rows))
+    parallel.barrier()
+    result = None
+    if not estimate_z_index:
+        if s.average_across_wells:
+            offsets = get_mean_z_positions(merged_path, method=s.average_across_wells_method, verbose=verbose)
+            try:
+                result = {"average": z_transforms_from_focus(offsets).tolist()}
+            except ValueError:
+                raise ValueError("Z index of focus reference is None; no valid (non-zero, non-NaN) z-index found in "
+                                 "z_drift_offsets") from None
+            if verbose and rank == 0:
+                print(f"Saving z focus shift matrices to {output_folder_path}")
+                np.save(output_folder_path / "z_focus_shift.npy", result["average"])
+        else:
+            result = {f.stem: np.load(f).tolist() for f in sorted(transforms_out.glob("*.npy"))}
+    parallel.barrier()
+    if rank == 0:
+        shutil.rmtree(focus_out)
+        shutil.rmtree(transforms_out)
+    return result
 
 
 def save_transforms(model, transforms, output_filepath_settings, output_filepath_plot=None, verbose: bool = False):

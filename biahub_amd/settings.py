@@ -188,9 +188,19 @@ class PhaseCrossCorrSettings(_Strict):
     Z_slice: list | Literal["all"] = "all"
 
 
+class FocusFindingSettings(_Strict):
+    """biahub/settings.py:217-221."""
+
+    average_across_wells: bool = False
+    average_across_wells_method: Literal["mean", "median"] = "mean"
+    skip_beads_fov: str = "0"
+    center_crop_xy: list[int] = [800, 800]
+
+
 class EstimateStabilizationSettings(_Strict):
-    """biahub/settings.py:295-310; only ``phase-cross-corr`` runs in this package, the other methods' sub-settings are
-    carried as plain dicts."""
+    """biahub/settings.py:295-310; ``phase-cross-corr`` (xyz) and ``focus-finding`` (z) run in this package.  The sub-settings
+    of the other methods are carried as plain dicts, and so is ``focus_finding_settings``, which is validated into
+    ``FocusFindingSettings`` where it is used."""
 
     stabilization_estimation_channel: str
     stabilization_channels: list

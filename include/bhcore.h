@@ -15,6 +15,8 @@
  *   bh_stitch_blend, bh_stitch_tile_lists
  *                          <- biahub/stitch.py:196-311 write_output_chunk (one chunk per mosaic)
  *   bh_stitch_edge_shifts  <- biahub/vendor/stitch/tile.py:126-160 offset, _dexp_shim.py:139-182 register_translation_nd
+ *   bh_focus_band_table, bh_focus_band_power
+ *                          <- biahub/estimate_stabilization.py:948 focus_from_transverse_band (waveorder focus.compute_midband_power)
  *   bh_valid_mask, bh_bits_and, bh_bits_unpack
  *                          <- biahub/estimate_crop.py:58-94 estimate_crop_one_position (masks, counts, their AND)
  *   bh_blosc_unfilter, bh_blosc_filter
@@ -221,6 +223,30 @@ int bh_stitch_tile_lists(int n_fov, const int64_t* offset_zyx, int64_t Z, int64_
 int bh_stitch_edge_shifts(bh_ctx* ctx, int n_edges, const void* const* tile_a, const void* const* tile_b, const int32_t* relation,
                           int dtype, int64_t Y, int64_t X, int64_t overlap, int flipud, int fliplr, double* shift,
                           double* confidence, float* const* prepared, float* const* corr_shifted);
+
+/* ---- focus finding (waveorder focus.compute_midband_power as the reference's estimate_stabilization.py:948, track.py:310 and
+ * estimate_registration.py:114-138 call it) ---------------------------------- */
+/* The annulus of a (Y, X) plane's spectrum: bin (ky, kx) with signed FFT indices s is in the band when
+ *     cutoff * frac_lo < sqrt((s_y / Y / pixel_size)^2 + (s_x / X / pixel_size)^2) < cutoff * frac_hi,   cutoff = 2 NA_det / lambda_ill,
+ * both comparisons strict and in float64.  kx_lo, kx_hi (HOST, Y entries each): row ky of the half spectrum (columns 0 .. X/2)
+ * holds the band's bins [kx_lo[ky], kx_hi[ky]) (kx_lo == kx_hi: none); n_bins (HOST) = the bins of the band in the full plane
+ * (0 is allowed).  Host only, no device.  BH_ERR_INVALID for a null pointer, Y or X odd or < 16 or beyond 2^31 - 1 elements per
+ * plane, non-finite or non-positive optics, and frac_lo >= frac_hi. */
+int bh_focus_band_table(int64_t Y, int64_t X, double pixel_size, double NA_det, double lambda_ill, double frac_lo, double frac_hi,
+                        int32_t* kx_lo, int32_t* kx_hi, int64_t* n_bins);
+
+/* power[z] = sum over the band of |fft2(v[z])| for the window v (Z, Y, X) that starts at `window` (device, `dtype`: uint8,
+ * uint16, int16 or float32; only read) inside a larger volume: element (z, y, x) is window[z * plane_stride + y * row_stride + x],
+ * strides in elements, so a centre window is read in place.  Slices are converted to float32 and transformed by batched float32
+ * hipFFT (as the reference's complex64 transform), |F| is summed in float64 over the band's half-spectrum intervals (columns
+ * 0 < kx < X/2 twice) in a fixed order: a repeated call returns the same bits.  power (HOST, Z doubles); sum (HOST, may be
+ * NULL) = the float64 sum of the window, exact for the integer dtypes.  max_batch <= 0: slices per transform chosen from a
+ * workspace bound of the call's own; > 0: at most that many.  Synchronises once, before the results are read.
+ * BH_ERR_INVALID before any device call for a null pointer, an unknown dtype, Z < 1, Y or X odd or < 16, row_stride < X,
+ * plane_stride < (Y - 1) * row_stride + X, a plane beyond 2^31 - 1 elements, and the table's conditions on the optics. */
+int bh_focus_band_power(bh_ctx* ctx, const void* window, int dtype, int64_t Z, int64_t Y, int64_t X, int64_t plane_stride,
+                        int64_t row_stride, double pixel_size, double NA_det, double lambda_ill, double frac_lo, double frac_hi,
+                        int max_batch, double* power, double* sum);
 
 /* ---- validity masks (crop estimation, biahub/estimate_crop.py:58-94) -------------------- */
 /* bits: ceil(n / 64) * 2 words on the device; voxel i -> bit i % 32 of word i / 32, set when the voxel is neither 0 nor
