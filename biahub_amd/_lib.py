@@ -22,6 +22,8 @@ BOUNDARY_ITK, BOUNDARY_SCIPY_CONSTANT, BOUNDARY_ZEROS = 0, 1, 2
 PCC_NORM = {None: 0, "magnitude": 1, "classic": 2}
 FILTER_F32, FILTER_BF16 = 0, 1
 DS_STRIDE, DS_MEAN, DS_MIN, DS_MAX, DS_MEDIAN, DS_MODE = range(6)
+PSF_NCOL, PSF_NGUESS = 55, 22  # BH_PSF_NCOL, BH_PSF_NGUESS
+PSF_CONVERGED, PSF_ITERCAP, PSF_NONFINITE, PSF_SINGULAR, PSF_EMPTY = range(5)
 (T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD) = range(9)
 
 _i64, _f64, _f32, _int, _vp = C.c_int64, C.c_double, C.c_float, C.c_int, C.c_void_p
@@ -117,6 +119,8 @@ SIGNATURES = {
     "bh_block_peaks": (_int, [_vp, _vp, _i64, _i64, _i64, _int, C.POINTER(_int), _vp, _vp, C.POINTER(_i64)]),
     "bh_patch_peaks": (_int, [_vp, _vp, _i64, _i64, _i64, C.POINTER(_int), _int, C.POINTER(_int), _f64, C.POINTER(_i64)]),
     "bh_average_patches": (_int, [_vp, _vp, _i64, _i64, _i64, C.POINTER(_int), _int, C.POINTER(_int), _int, _vp]),
+    "bh_psf_fit": (_int, [_vp, _vp, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), _int, C.POINTER(_f64), _f64, _f64, _int, _int,
+                          C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_int), C.POINTER(_int)]),
     "bh_affine": (_int, [_vp, _vp, _int, _i64, _i64, _i64, C.POINTER(_f64), _int, _int, _f32, _vp, _i64, _i64,
                          _i64, C.POINTER(_i64)]),
     "bh_spline_prefilter": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp]),

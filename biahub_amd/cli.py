@@ -769,6 +769,34 @@ def estimate_psf_cli(input_position_dirpaths, config_filepath, output_dirpath):
     click.echo(f"PSF saved to {Path(output_dirpath).resolve()}")
 
 
+@cli.command("characterize-psf")
+@click.option("--input-position-dirpaths", "-i", multiple=True, required=True, callback=_positions)
+@_config
+@click.option("--output-dirpath", "-o", required=True, type=click.Path(path_type=Path))
+def characterize_psf_cli(input_position_dirpaths, config_filepath, output_dirpath):
+    """Characterize the PSF from a bead volume: Gaussian fits and 1-D widths of every bead, CSV tables, plots and a report
+    in the output directory (reference: ``biahub characterize-psf``, characterize_psf.py:791-822).  (t, c) = (0, 0) of the
+    first position; the fits run on the GPU."""
+    import warnings
+
+    from .characterize_psf import SUPPORTED_DTYPES, characterize_psf
+    from .settings import CharacterizeSettings
+
+    if len(input_position_dirpaths) > 1:
+        warnings.warn("Only the first position will be characterized.", stacklevel=2)
+    settings = yaml_to_model(config_filepath, CharacterizeSettings)
+    position = Path(input_position_dirpaths[0])
+    dataset_name = position.parts[-4]
+    click.echo("Loading data...")
+    with open_ome_zarr(position) as ds:
+        if np.dtype(ds.data.dtype) not in SUPPORTED_DTYPES:
+            raise click.ClickException(f"characterize-psf reads uint8, uint16, int16 and float32 stores: float32 cannot hold "
+                                       f"{np.dtype(ds.data.dtype)} exactly")
+        zyx_data = ds.data[0, 0]
+        zyx_scale = tuple(ds.scale[-3:])
+    characterize_psf(zyx_data, zyx_scale, settings, Path(output_dirpath), str(position), dataset_name, echo=click.echo)
+
+
 @cli.command("concatenate")
 @_config
 @click.option("--output-dirpath", "-o", required=True, type=click.Path(path_type=Path),

@@ -174,6 +174,25 @@ class PsfFromBeadsSettings(_Strict):
     axis2_patch_size: PositiveInt = 101
 
 
+class CharacterizeSettings(_Strict):
+    """biahub/settings.py:430-449.  ``device`` is kept as given: there is no CPU path to fall back to."""
+
+    block_size: list[NonNegativeInt] = (64, 64, 32)
+    blur_kernel_size: NonNegativeInt = 3
+    nms_distance: NonNegativeInt = 32
+    min_distance: NonNegativeInt = 50
+    threshold_abs: PositiveFloat = 200.0
+    max_num_peaks: NonNegativeInt = 2000
+    exclude_border: list[NonNegativeInt] = (5, 10, 5)
+    device: str = "cuda"
+    patch_size: tuple[PositiveFloat, PositiveFloat, PositiveFloat] | None = None
+    axis_labels: list[str] = ["AXIS0", "AXIS1", "AXIS2"]
+    offset: float = 0.0
+    gain: float = 1.0
+    use_robust_1d_fwhm: bool = False
+    fwhm_plot_type: Literal["1D", "3D"] = "3D"
+
+
 class PhaseCrossCorrSettings(_Strict):
     """biahub/settings.py:205-214."""
 

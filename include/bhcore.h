@@ -41,6 +41,8 @@
  *   bh_patch_peaks, bh_average_patches
  *                          <- biahub/estimate_psf.py:84-112 (extract_beads + normalised mean),
  *                             vendor/napari_psf_analysis/psf_analysis/extract/BeadExtractor.py:36-78
+ *   bh_psf_fit             <- biahub/characterize_psf.py:193-272 analyze_psf (its per-bead loop: the three curve_fit calls of
+ *                             vendor/napari_psf_analysis/psf_analysis/fit/fitter.py and their initial guesses, estimator.py)
  *   bh_affine              <- biahub/register.py:202-281 apply_affine_transform,
  *                             biahub/stabilize.py:32-90 apply_stabilization_transform,
  *                             biahub/core/transform.py:374-396 Transform._apply_scipy
@@ -531,6 +533,38 @@ int bh_patch_peaks(bh_ctx* ctx, const float* in, int64_t Z, int64_t Y, int64_t X
  * out -= min(out); out /= max(out) (estimate_psf.py:104-112).  Synchronises. */
 int bh_average_patches(bh_ctx* ctx, const float* in, int64_t Z, int64_t Y, int64_t X, const int* starts, int n,
                        const int patch[3], int normalise, float* out);
+
+/* The three Gaussian fits of analyze_psf (biahub/characterize_psf.py:193-272 -> vendor/napari_psf_analysis PSF.analyze) for
+ * n beads in one batched solve.  Bead b is the box [starts[3b..], starts + shapes[3b..]) of the float32 device volume (host
+ * int arrays; boxes may differ in shape, as the reference's crops do at the far border; every box must lie inside the
+ * volume and satisfy voxels * longest_axis^2 < 2^32).  The sample is v = (int32) max((x + offset) * gain, 0), truncated;
+ * float32_math != 0 evaluates (x + offset) * gain in float32, as NumPy does for a float32 store, otherwise in float64.
+ * Per bead and fit (0: z column through the centre, 1: centre yx plane, 2: whole patch; centres are shape / 2) the
+ * reference's initial guess (fit/estimator.py: uint16 median, max - median, weighted centroid, diagonal of
+ * np.cov(fweights)) starts a float64 Levenberg-Marquardt solve with the analytic Jacobian (csrc/psffit.hip).
+ * All outputs are HOST arrays:
+ *   rows        n x BH_PSF_NCOL    the columns of PSF.get_summary_dict(): ZFitRecord (9), YXFitRecord (18), ZYXFitRecord (28)
+ *                                  in that order, standard errors as scipy's curve_fit(absolute_sigma=False) defines them,
+ *                                  yx_cxx_sde = the error of cyx as the reference writes it; coordinates are patch-local
+ *                                  (index * spacing), amplitudes in sample units
+ *   guesses     n x BH_PSF_NGUESS  the initial parameters: z (4: bg, amp, mu, sigma), yx (7), zyx (11)
+ *   status      n x 3              BH_PSF_CONVERGED, _ITERCAP (max_iterations passes spent), _NONFINITE (a non-finite guess
+ *                                  or residual, or a median >= 65536 where the reference's uint16 cast wraps), _SINGULAR
+ *                                  (J^T J not positive definite, or no more samples than parameters), _EMPTY (sum of the
+ *                                  sample is 0)
+ *   iterations  n x 3              passes over the sample after the first
+ * A fit that did not converge has NaN in its own columns and leaves every other fit and bead untouched.  The result is
+ * bit-reproducible (fixed-order reductions, no float atomics).  Synchronises. */
+#define BH_PSF_NCOL 55
+#define BH_PSF_NGUESS 22
+#define BH_PSF_CONVERGED 0
+#define BH_PSF_ITERCAP 1
+#define BH_PSF_NONFINITE 2
+#define BH_PSF_SINGULAR 3
+#define BH_PSF_EMPTY 4
+int bh_psf_fit(bh_ctx* ctx, const float* in, int64_t Z, int64_t Y, int64_t X, const int* starts, const int* shapes, int n,
+               const double spacing[3], double offset, double gain, int float32_math, int max_iterations, double* rows,
+               double* guesses, int* status, int* iterations);
 
 /* ---- affine warp ------------------------------------------------------------------- */
 /* out(p) = in(M p), M = 3x4 row-major pull matrix (rows z,y,x; last column translation) in ZYX
