@@ -54,22 +54,45 @@ void set_error(const char* fmt, ...);
 
 enum TimerSlot { T_DESKEW = 0, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_COUNT };
 
-// Library plans of the 3-D real transform of a (Z, Y, X) volume.  Shapes with a non-power-of-two extent (what reaches the
-// library in production: the fused engine in fftconv.hip takes the power-of-two ones) use hipfftPlan3d.  All-power-of-two
-// shapes (only here when BH_FFT_BACKEND=hipfft forces it, or beyond the engine's size limits) are decomposed into batched
-// 1-D real transforms along x and one strided batched 2-D complex transform over (z, y): rocFFT 1.0.36 (ROCm 7.2) returns
-// wrong 3-D real transforms for some power-of-two shapes once 3-D plans of certain other power-of-two shapes exist in the
-// process (tools/hipfft_two_plans.cpp; tools/hipfft_plan3d_sweep.cpp: 8 of 131 power-of-two plans wrong, 0 of 319
-// mixed-radix ones); the decomposition is immune (tools/hipfft_separable_probe.cpp) but ~2.5x slower at large sizes.
+// One hipFFT plan.  `volume`: the 3-D real transform of (n[0], n[1], n[2]) through hipfftMakePlan3d (the entry point the
+// self-check of get_plans exists for), `type` R2C or C2R.  Otherwise one hipfftMakePlanMany call, the members in the order of
+// its arguments; with `embed`, n is passed as inembed and onembed too (hipFFT reads strides and distances only then).
+struct FftDesc {
+    bool volume = false;
+    int rank = 3;
+    int64_t n[3] = {0, 0, 0};
+    bool embed = false;
+    int64_t istride = 1, idist = 0, ostride = 1, odist = 0;
+    hipfftType type = HIPFFT_R2C;
+    int64_t batch = 1;
+};
+// `batch` contiguous images of (n0, n1), real <-> half spectrum of (n0, n1/2+1): type R2C, C2R, D2Z or Z2D
+inline FftDesc fft_batched_2d(hipfftType type, int64_t batch, int64_t n0, int64_t n1) {
+    const bool forward = type == HIPFFT_R2C || type == HIPFFT_D2Z;
+    const int64_t real = n0 * n1, spec = n0 * (n1 / 2 + 1);
+    return FftDesc{false, 2, {n0, n1}, false, 1, forward ? real : spec, 1, forward ? spec : real, type, batch};
+}
+
+enum { FFT_FWD = 0, FFT_INV = 1, FFT_ZY = 2, FFT_MAX_PLANS = 3 };  // slots of FftPlans::h
+// A cached set of up to three plans (build_plans): one work area from dev_alloc shared by all of them (they never run
+// concurrently on one stream), auto-allocation off, every handle on the context's stream.  h[] is in the order of the
+// descriptions the set was built from, unused slots 0; by convention the forward transform first, its inverse second.
+// Volume sets, the 3-D real transform of (Z, Y, X): shapes with a non-power-of-two extent (what reaches the library in
+// production: the fused engine in fftconv.hip takes the power-of-two ones) use hipfftPlan3d.  All-power-of-two shapes (only
+// here when BH_FFT_BACKEND=hipfft forces it, or beyond the engine's size limits) are decomposed into batched 1-D real
+// transforms along x and one strided batched 2-D complex transform over (z, y): rocFFT 1.0.36 (ROCm 7.2) returns wrong 3-D
+// real transforms for some power-of-two shapes once 3-D plans of certain other power-of-two shapes exist in the process
+// (tools/hipfft_two_plans.cpp; tools/hipfft_plan3d_sweep.cpp: 8 of 131 power-of-two plans wrong, 0 of 319 mixed-radix ones);
+// the decomposition is immune (tools/hipfft_separable_probe.cpp) but ~2.5x slower at large sizes.
 struct FftPlans {
-    bool separable = false;
-    hipfftHandle r2c = 0, c2r = 0;  // 3-D plans (separable == false)
-    hipfftHandle xr = 0;            // x: Z*Y rows, real X -> complex X/2+1
-    hipfftHandle xi = 0;            // x: complex X/2+1 -> real X
-    hipfftHandle zy = 0;            // (z, y): complex, element stride X/2+1, one batch entry per x
+    bool separable = false;  // volume sets: the decomposed triple (volume_descs in context.hip) instead of the 3-D pair
+    hipfftHandle h[FFT_MAX_PLANS] = {};
     void* work = nullptr;
     size_t work_bytes = 0;
 };
+// What a cached set transforms: its family and the family's integers (volume: Z, Y, X; strips and slices: batch, n0, n1).
+enum class FftFamily { Volume, StripsF64, SlicesF32 };
+using FftKey = std::tuple<FftFamily, int64_t, int64_t, int64_t>;
 
 // Named, grow-only device scratch buffers owned by the context.
 struct Scratch {
@@ -86,7 +109,7 @@ struct bh_ctx {
     hipEvent_t ev[2 * bh::T_COUNT] = {};
     bool ev_valid[bh::T_COUNT] = {};
     float ms_override[bh::T_COUNT] = {};
-    std::map<std::tuple<int64_t, int64_t, int64_t>, bh::FftPlans> plans;
+    std::map<bh::FftKey, bh::FftPlans> plans;  // owned by context.hip: cached_plans, destroy_plans, stream_plans
     std::map<std::string, bh::Scratch> scratch;
     int num_cus = 256;
     int deskew_path = 0;     // how the last bh_deskew filled the overhang: 0 mask pipeline (or no fill), 1 one-pass (deskew_rows.inc)
@@ -117,6 +140,10 @@ hipError_t dev_alloc(int device, size_t bytes, void** out);
 hipError_t dev_free(void* p);
 bool dev_alloc_is_shuffled();  // the default layout is in force (not switched off by BH_ALLOC_VMM_MB=0)
 bool dev_block_is_vmm(const void* p);  // this block was built from mapped chunks (large enough for the layout)
+// The set cached under `key`, or built from the n (1 to 3) descriptions and inserted.  All or nothing: on failure nothing is
+// left behind, the status is BH_ERR_INVALID (a value that does not fit hipFFT's int), BH_ERR_NOMEM or BH_ERR_HIP, and the
+// message names `who` and the transform.
+int cached_plans(bh_ctx* ctx, const char* who, const FftKey& key, const FftDesc* descs, int n, FftPlans** out);
 int get_plans(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, FftPlans** out);
 // real (Z,Y,X) -> half spectrum (Z,Y,X/2+1), unnormalised
 int fft_forward(const FftPlans* pl, const float* real, float2* spec);

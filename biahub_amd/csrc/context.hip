@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include <atomic>
+#include <climits>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -276,50 +277,87 @@ __global__ void check_compare_kernel(const float* x, int64_t n, float inv_n, uns
     atomicMax(worst, __float_as_uint(m));  // non-negative floats order like their bit patterns
 }
 
-static void destroy_handles(FftPlans& p) {
-    for (hipfftHandle* h : {&p.r2c, &p.c2r, &p.xr, &p.xi, &p.zy})
-        if (*h) {
-            hipfftDestroy(*h);
-            *h = 0;
-        }
+// ---- the owner of every cached plan set ----------------------------------------------------------------------------
+static void destroy_plans(FftPlans& p) {
+    for (hipfftHandle h : p.h)
+        if (h) (void)hipfftDestroy(h);
     if (p.work) (void)dev_free(p.work);
-    p.work = nullptr;
-    p.work_bytes = 0;
+    p = FftPlans();
 }
 
-static int make_handles(bh_ctx* ctx, FftPlans& p, int64_t Z, int64_t Y, int64_t X) {
-    hipfftHandle* hs[3] = {&p.r2c, &p.c2r, nullptr};
-    size_t ws[3] = {0, 0, 0};
-    int nh = 2;
-    if (p.separable) {
-        BH_REQUIRE(Z * Y < (1ll << 31), "FFT batch %lld too large", (long long)(Z * Y));
-        hs[0] = &p.xr, hs[1] = &p.xi, hs[2] = &p.zy;
-        nh = 3;
-    }
-    for (int i = 0; i < nh; ++i) {
-        BH_CHECK_FFT(hipfftCreate(hs[i]));
-        BH_CHECK_FFT(hipfftSetAutoAllocation(*hs[i], 0));
-    }
-    if (p.separable) {
-        const int Xh = (int)(X / 2 + 1);
-        int nx[1] = {(int)X}, nzy[2] = {(int)Z, (int)Y};
-        BH_CHECK_FFT(hipfftMakePlanMany(p.xr, 1, nx, nullptr, 1, (int)X, nullptr, 1, Xh, HIPFFT_R2C, (int)(Z * Y), &ws[0]));
-        BH_CHECK_FFT(hipfftMakePlanMany(p.xi, 1, nx, nullptr, 1, Xh, nullptr, 1, (int)X, HIPFFT_C2R, (int)(Z * Y), &ws[1]));
-        BH_CHECK_FFT(hipfftMakePlanMany(p.zy, 2, nzy, nzy, Xh, 1, nzy, Xh, 1, HIPFFT_C2C, Xh, &ws[2]));
-    } else {
-        BH_CHECK_FFT(hipfftMakePlan3d(p.r2c, (int)Z, (int)Y, (int)X, HIPFFT_R2C, &ws[0]));
-        BH_CHECK_FFT(hipfftMakePlan3d(p.c2r, (int)Z, (int)Y, (int)X, HIPFFT_C2R, &ws[1]));
-    }
-    for (int i = 0; i < nh; ++i)
-        if (ws[i] > p.work_bytes) p.work_bytes = ws[i];
-    // one work area shared by all plans of the shape (they never run concurrently on one stream)
-    if (p.work_bytes) BH_CHECK_HIP(dev_alloc(ctx->device, p.work_bytes, &p.work));
-    for (int i = 0; i < nh; ++i) {
-        if (p.work_bytes) BH_CHECK_FFT(hipfftSetWorkArea(*hs[i], p.work));
-        BH_CHECK_FFT(hipfftSetStream(*hs[i], ctx->stream));
-    }
+static int stream_plans(const FftPlans& p, hipStream_t s) {
+    for (hipfftHandle h : p.h)
+        if (h) BH_CHECK_FFT(hipfftSetStream(h, s));
     return BH_OK;
 }
+
+static int build_plans(bh_ctx* ctx, const char* who, const FftDesc* descs, int n, FftPlans* out) {
+    BH_REQUIRE(n >= 1 && n <= FFT_MAX_PLANS, "%s: %d FFT plans in one set (1 to %d)", who, n, FFT_MAX_PLANS);
+    char what[FFT_MAX_PLANS][160];  // "24 transforms of (300, 2048), hipfftType 0x6a": at most 124 characters
+    for (int i = 0; i < n; ++i) {
+        const FftDesc& d = descs[i];
+        bool fits = d.rank >= 1 && d.rank <= 3 && d.batch >= 1;  // hipFFT takes int
+        int len = snprintf(what[i], sizeof(what[i]), "%lld transform%s of (", (long long)d.batch, d.batch == 1 ? "" : "s");
+        for (int a = 0; a < d.rank && a < 3; ++a) {
+            fits = fits && d.n[a] >= 1;
+            len += snprintf(what[i] + len, sizeof(what[i]) - len, a ? ", %lld" : "%lld", (long long)d.n[a]);
+        }
+        snprintf(what[i] + len, sizeof(what[i]) - len, "), hipfftType 0x%x", (unsigned)d.type);
+        for (int64_t v : {d.n[0], d.n[1], d.n[2], d.istride, d.idist, d.ostride, d.odist, d.batch}) fits = fits && v >= 0 && v <= (int64_t)INT_MAX;
+        BH_REQUIRE(fits, "%s: %s does not fit hipFFT's int arguments", who, what[i]);
+    }
+    FftPlans p;
+    auto fail = [&](int code) {
+        destroy_plans(p);
+        return code;
+    };
+    for (int i = 0; i < n; ++i)
+        if (hipfftCreate(&p.h[i]) != HIPFFT_SUCCESS || hipfftSetAutoAllocation(p.h[i], 0) != HIPFFT_SUCCESS) {
+            set_error("%s: hipfftCreate failed", who);
+            return fail(BH_ERR_HIP);
+        }
+    for (int i = 0; i < n; ++i) {
+        const FftDesc& d = descs[i];
+        int dims[3] = {(int)d.n[0], (int)d.n[1], (int)d.n[2]};
+        size_t ws = 0;
+        const hipfftResult r =
+            d.volume ? hipfftMakePlan3d(p.h[i], dims[0], dims[1], dims[2], d.type, &ws)
+                     : hipfftMakePlanMany(p.h[i], d.rank, dims, d.embed ? dims : nullptr, (int)d.istride, (int)d.idist, d.embed ? dims : nullptr,
+                                          (int)d.ostride, (int)d.odist, d.type, (int)d.batch, &ws);
+        if (r != HIPFFT_SUCCESS) {
+            set_error("%s: no hipFFT plan for %s (hipfftResult %d)", who, what[i], (int)r);
+            return fail(r == HIPFFT_ALLOC_FAILED ? BH_ERR_NOMEM : BH_ERR_HIP);
+        }
+        p.work_bytes = std::max(p.work_bytes, ws);
+    }
+    if (p.work_bytes && dev_alloc(ctx->device, p.work_bytes, &p.work) != hipSuccess) {
+        (void)hipGetLastError();
+        p.work = nullptr;
+        set_error("%s: %zu bytes of FFT work area for %s", who, p.work_bytes, what[0]);
+        return fail(BH_ERR_NOMEM);
+    }
+    bool ok = true;
+    for (int i = 0; i < n && p.work_bytes; ++i) ok = ok && hipfftSetWorkArea(p.h[i], p.work) == HIPFFT_SUCCESS;
+    if (!ok || stream_plans(p, ctx->stream) != BH_OK) {
+        set_error("%s: hipFFT plan set-up failed for %s", who, what[0]);
+        return fail(BH_ERR_HIP);
+    }
+    *out = p;
+    return BH_OK;
+}
+
+int cached_plans(bh_ctx* ctx, const char* who, const FftKey& key, const FftDesc* descs, int n, FftPlans** out) {
+    auto it = ctx->plans.find(key);
+    if (it == ctx->plans.end()) {
+        FftPlans p;
+        BH_TRY(build_plans(ctx, who, descs, n, &p));
+        it = ctx->plans.emplace(key, p).first;
+    }
+    *out = &it->second;
+    return BH_OK;
+}
+
+static const float PLAN_CHECK_TOL = 1e-3f;  // a sound float32 round trip of values in [0, 1) errs by ~1e-6; a bad plan by ~1
 
 // round trip on the context's own scratch (the buffers the caller is about to use at this size anyway)
 static int plan_round_trip_error(bh_ctx* ctx, const FftPlans& p, int64_t Z, int64_t Y, int64_t X, float* err) {
@@ -345,60 +383,73 @@ static int plan_round_trip_error(bh_ctx* ctx, const FftPlans& p, int64_t Z, int6
     return BH_OK;
 }
 
+// the descriptions of a volume set: the 3-D pair, or the decomposed triple (x rows forward, x rows back, (z, y) in place)
+static int volume_descs(bool separable, int64_t Z, int64_t Y, int64_t X, FftDesc* d) {
+    const int64_t Xh = X / 2 + 1;
+    if (!separable) {
+        d[FFT_FWD] = d[FFT_INV] = FftDesc{true, 3, {Z, Y, X}};
+        d[FFT_INV].type = HIPFFT_C2R;
+        return 2;
+    }
+    d[FFT_FWD] = FftDesc{false, 1, {X}, false, 1, X, 1, Xh, HIPFFT_R2C, Z * Y};
+    d[FFT_INV] = FftDesc{false, 1, {X}, false, 1, Xh, 1, X, HIPFFT_C2R, Z * Y};
+    d[FFT_ZY] = FftDesc{false, 2, {Z, Y}, true, Xh, 1, Xh, 1, HIPFFT_C2C, Xh};
+    return 3;
+}
+
+// Builds the volume set of one kind into the cache and, unless BH_FFT_NOCHECK is set, runs its self-check.  Only a set that
+// passes stays: after an error, or with *err at or above the tolerance (the status is BH_OK then), nothing is left behind.
+static int checked_volume_plans(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, bool separable, float* err, FftPlans** out) {
+    const FftKey key{FftFamily::Volume, Z, Y, X};
+    BH_REQUIRE(!separable || Z * Y < (1ll << 31), "FFT batch %lld too large", (long long)(Z * Y));
+    FftDesc d[FFT_MAX_PLANS];
+    const int n = volume_descs(separable, Z, Y, X, d);
+    BH_TRY(cached_plans(ctx, "get_plans", key, d, n, out));
+    (*out)->separable = separable;
+    *err = 0.0f;
+    if (getenv("BH_FFT_NOCHECK") != nullptr) return BH_OK;
+    const int st = plan_round_trip_error(ctx, **out, Z, Y, X, err);
+    if (st != BH_OK || !(*err < PLAN_CHECK_TOL)) {
+        destroy_plans(**out);
+        ctx->plans.erase(key);
+        *out = nullptr;
+    }
+    return st;
+}
+
 int get_plans(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, FftPlans** out) {
-    auto key = std::make_tuple(Z, Y, X);
-    auto it = ctx->plans.find(key);
+    auto it = ctx->plans.find(FftKey{FftFamily::Volume, Z, Y, X});  // a hit needs none of the rules below
     if (it != ctx->plans.end()) {
         *out = &it->second;
         return BH_OK;
     }
     BH_REQUIRE(Z > 0 && Y > 0 && X > 0 && Z < (1ll << 31) && Y < (1ll << 31) && X < (1ll << 31),
                "invalid FFT shape (%lld,%lld,%lld)", (long long)Z, (long long)Y, (long long)X);
-    FftPlans p;
     auto pow2 = [](int64_t n) { return (n & (n - 1)) == 0; };
-    p.separable = getenv("BH_FFT_SEPARABLE") != nullptr || (pow2(Z) && pow2(Y) && pow2(X));
-    const bool check = getenv("BH_FFT_NOCHECK") == nullptr;
-    const float tol = 1e-3f;  // a sound float32 round trip of values in [0, 1) errs by ~1e-6; a bad plan by ~1
+    const bool separable = getenv("BH_FFT_SEPARABLE") != nullptr || (pow2(Z) && pow2(Y) && pow2(X));
     float err = 0.0f;
-    BH_TRY(make_handles(ctx, p, Z, Y, X));
-    if (check) {
-        BH_TRY(plan_round_trip_error(ctx, p, Z, Y, X, &err));
-        if (!(err < tol) && !p.separable) {
-            destroy_handles(p);
-            p.separable = true;
-            BH_TRY(make_handles(ctx, p, Z, Y, X));
-            BH_TRY(plan_round_trip_error(ctx, p, Z, Y, X, &err));
-            ++ctx->plans_replaced;
-        }
-        if (!(err < tol)) {
-            destroy_handles(p);
-            set_error("hipFFT plan for (%lld,%lld,%lld) fails its round-trip self-check (error %g): the FFT library is "
-                      "returning wrong transforms", (long long)Z, (long long)Y, (long long)X, (double)err);
-            return BH_ERR_HIP;
-        }
+    BH_TRY(checked_volume_plans(ctx, Z, Y, X, separable, &err, out));
+    if (!(err < PLAN_CHECK_TOL) && !separable) {
+        BH_TRY(checked_volume_plans(ctx, Z, Y, X, true, &err, out));
+        ++ctx->plans_replaced;
     }
-    auto ins = ctx->plans.emplace(key, p);
-    *out = &ins.first->second;
+    if (!(err < PLAN_CHECK_TOL)) {
+        set_error("hipFFT plan for (%lld,%lld,%lld) fails its round-trip self-check (error %g): the FFT library is "
+                  "returning wrong transforms", (long long)Z, (long long)Y, (long long)X, (double)err);
+        return BH_ERR_HIP;
+    }
     return BH_OK;
 }
 
 int fft_forward(const FftPlans* pl, const float* real, float2* spec) {
-    if (!pl->separable) {
-        BH_CHECK_FFT(hipfftExecR2C(pl->r2c, const_cast<float*>(real), (hipfftComplex*)spec));
-        return BH_OK;
-    }
-    BH_CHECK_FFT(hipfftExecR2C(pl->xr, const_cast<float*>(real), (hipfftComplex*)spec));
-    BH_CHECK_FFT(hipfftExecC2C(pl->zy, (hipfftComplex*)spec, (hipfftComplex*)spec, HIPFFT_FORWARD));
+    BH_CHECK_FFT(hipfftExecR2C(pl->h[FFT_FWD], const_cast<float*>(real), (hipfftComplex*)spec));
+    if (pl->separable) BH_CHECK_FFT(hipfftExecC2C(pl->h[FFT_ZY], (hipfftComplex*)spec, (hipfftComplex*)spec, HIPFFT_FORWARD));
     return BH_OK;
 }
 
 int fft_inverse(const FftPlans* pl, float2* spec, float* real) {
-    if (!pl->separable) {
-        BH_CHECK_FFT(hipfftExecC2R(pl->c2r, (hipfftComplex*)spec, real));
-        return BH_OK;
-    }
-    BH_CHECK_FFT(hipfftExecC2C(pl->zy, (hipfftComplex*)spec, (hipfftComplex*)spec, HIPFFT_BACKWARD));
-    BH_CHECK_FFT(hipfftExecC2R(pl->xi, (hipfftComplex*)spec, real));
+    if (pl->separable) BH_CHECK_FFT(hipfftExecC2C(pl->h[FFT_ZY], (hipfftComplex*)spec, (hipfftComplex*)spec, HIPFFT_BACKWARD));
+    BH_CHECK_FFT(hipfftExecC2R(pl->h[FFT_INV], (hipfftComplex*)spec, real));
     return BH_OK;
 }
 
@@ -480,11 +531,7 @@ int bh_ctx_release_workspace(bh_ctx* ctx) {
     BH_REQUIRE(ctx != nullptr, "ctx is NULL");
     BH_CHECK_HIP(hipSetDevice(ctx->device));
     BH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    for (auto& kv : ctx->plans) {
-        for (hipfftHandle h : {kv.second.r2c, kv.second.c2r, kv.second.xr, kv.second.xi, kv.second.zy})
-            if (h) hipfftDestroy(h);
-        if (kv.second.work) (void)bh::dev_free(kv.second.work);
-    }
+    for (auto& kv : ctx->plans) bh::destroy_plans(kv.second);
     ctx->plans.clear();
     bh::rl_oneshot_drop(ctx);
     for (auto& kv : ctx->scratch)
@@ -521,10 +568,7 @@ int bh_ctx_destroy(bh_ctx* ctx) {
 int bh_ctx_set_stream(bh_ctx* ctx, void* hip_stream) {
     BH_REQUIRE(ctx != nullptr, "ctx is NULL");
     ctx->stream = (hipStream_t)hip_stream;
-    for (auto& kv : ctx->plans) {
-        for (hipfftHandle h : {kv.second.r2c, kv.second.c2r, kv.second.xr, kv.second.xi, kv.second.zy})
-            if (h) BH_CHECK_FFT(hipfftSetStream(h, ctx->stream));
-    }
+    for (auto& kv : ctx->plans) BH_TRY(bh::stream_plans(kv.second, ctx->stream));
     return BH_OK;
 }
 

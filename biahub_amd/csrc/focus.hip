@@ -161,46 +161,10 @@ __global__ __launch_bounds__(256) void focus_band_slices_kernel(const double* __
     if (threadIdx.x == 0) power[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// The batched 2-D real float32 plan of nb (Y, X) slices, kept in the context's plan cache under a key no volume shape and no
-// strip batch uses.  The cache's owner releases and re-streams it with its other plans.
+// The batched 2-D real float32 plan of nb (Y, X) slices: one cached set per (nb, Y, X), so a shorter last chunk has its own.
 static int get_focus_plan(bh_ctx* ctx, int64_t nb, int64_t Y, int64_t X, FftPlans** out) {
-    const auto key = std::make_tuple(-((int64_t)1 << 40) - nb, Y, X);
-    auto it = ctx->plans.find(key);
-    if (it != ctx->plans.end()) {
-        *out = &it->second;
-        return BH_OK;
-    }
-    FftPlans p;
-    auto fail = [&](int code) {
-        if (p.r2c) hipfftDestroy(p.r2c);
-        if (p.work) (void)dev_free(p.work);
-        return code;
-    };
-    if (hipfftCreate(&p.r2c) != HIPFFT_SUCCESS || hipfftSetAutoAllocation(p.r2c, 0) != HIPFFT_SUCCESS) {
-        set_error("bh_focus_band_power: hipfftCreate failed");
-        return fail(BH_ERR_HIP);
-    }
-    int dims[2] = {(int)Y, (int)X};
-    const int nh = (int)(X / 2 + 1);
-    size_t ws = 0;
-    if (hipfftMakePlanMany(p.r2c, 2, dims, nullptr, 1, (int)(Y * X), nullptr, 1, (int)(Y * nh), HIPFFT_R2C, (int)nb, &ws) != HIPFFT_SUCCESS) {
-        set_error("bh_focus_band_power: no hipFFT plan for %lld slices of (%lld, %lld)", (long long)nb, (long long)Y, (long long)X);
-        return fail(BH_ERR_HIP);
-    }
-    p.work_bytes = ws;
-    if (ws && dev_alloc(ctx->device, ws, &p.work) != hipSuccess) {
-        (void)hipGetLastError();
-        p.work = nullptr;
-        set_error("bh_focus_band_power: %zu bytes of FFT work area", ws);
-        return fail(BH_ERR_NOMEM);
-    }
-    if ((ws && hipfftSetWorkArea(p.r2c, p.work) != HIPFFT_SUCCESS) || hipfftSetStream(p.r2c, ctx->stream) != HIPFFT_SUCCESS) {
-        set_error("bh_focus_band_power: hipFFT plan set-up failed");
-        return fail(BH_ERR_HIP);
-    }
-    auto ins = ctx->plans.emplace(key, p);
-    *out = &ins.first->second;
-    return BH_OK;
+    const FftDesc d = fft_batched_2d(HIPFFT_R2C, nb, Y, X);
+    return cached_plans(ctx, "bh_focus_band_power", FftKey{FftFamily::SlicesF32, nb, Y, X}, &d, 1, out);
 }
 
 template <typename TI>
@@ -280,7 +244,7 @@ extern "C" int bh_focus_band_power(bh_ctx* ctx, const void* window, int dtype, i
         if (!nr) continue;
         FftPlans* pl = nullptr;
         BH_TRY(get_focus_plan(ctx, nz, Y, X, &pl));
-        BH_CHECK_FFT(hipfftExecR2C(pl->r2c, d_real, (hipfftComplex*)d_spec));
+        BH_CHECK_FFT(hipfftExecR2C(pl->h[FFT_FWD], d_real, (hipfftComplex*)d_spec));
         hipLaunchKernelGGL(focus_band_rows_kernel, dim3((unsigned)ceil_div(nr, 4), (unsigned)nz), dim3(256), 0, s, (const float2*)d_spec,
                            (const BandRow*)d_rows, nr, (int)Y, (int)nh, (int)(X / 2), d_rowpart);
         hipLaunchKernelGGL(focus_band_slices_kernel, dim3((unsigned)nz), dim3(256), 0, s, (const double*)d_rowpart, nr, d_out + z0);

@@ -329,52 +329,11 @@ __global__ __launch_bounds__(256) void peak_background_kernel(const PeakGeom p, 
     }
 }
 
-// Batched 2-D real float64 plans of (n0, n1) strips, kept in the context's plan cache under the key (-n_edges, n0, n1): r2c transforms
-// the 2 n_edges strips, c2r the n_edges cross-power spectra.  The cache's owner releases and re-streams them with its 3-D plans.
+// Batched 2-D real float64 plans of (n0, n1) strips, one cached set per (n_edges, n0, n1): FFT_FWD transforms the 2 n_edges strips,
+// FFT_INV the n_edges cross-power spectra.
 static int get_strip_plans(bh_ctx* ctx, int64_t n_edges, int64_t n0, int64_t n1, FftPlans** out) {
-    const auto key = std::make_tuple(-n_edges, n0, n1);
-    auto it = ctx->plans.find(key);
-    if (it != ctx->plans.end()) {
-        *out = &it->second;
-        return BH_OK;
-    }
-    FftPlans p;
-    size_t ws[2] = {0, 0};
-    int dims[2] = {(int)n0, (int)n1};
-    auto fail = [&](int code) {
-        for (hipfftHandle* h : {&p.r2c, &p.c2r})
-            if (*h) hipfftDestroy(*h);
-        if (p.work) (void)dev_free(p.work);
-        return code;
-    };
-    for (hipfftHandle* h : {&p.r2c, &p.c2r}) {
-        if (hipfftCreate(h) != HIPFFT_SUCCESS || hipfftSetAutoAllocation(*h, 0) != HIPFFT_SUCCESS) {
-            set_error("bh_stitch_edge_shifts: hipfftCreate failed");
-            return fail(BH_ERR_HIP);
-        }
-    }
-    const int nh = (int)(n1 / 2 + 1);
-    if (hipfftMakePlanMany(p.r2c, 2, dims, nullptr, 1, (int)(n0 * n1), nullptr, 1, (int)(n0 * nh), HIPFFT_D2Z, (int)(2 * n_edges), &ws[0]) != HIPFFT_SUCCESS ||
-        hipfftMakePlanMany(p.c2r, 2, dims, nullptr, 1, (int)(n0 * nh), nullptr, 1, (int)(n0 * n1), HIPFFT_Z2D, (int)n_edges, &ws[1]) != HIPFFT_SUCCESS) {
-        set_error("bh_stitch_edge_shifts: no hipFFT plan for %lld strips of (%lld, %lld)", (long long)(2 * n_edges), (long long)n0, (long long)n1);
-        return fail(BH_ERR_HIP);
-    }
-    p.work_bytes = std::max(ws[0], ws[1]);
-    if (p.work_bytes && dev_alloc(ctx->device, p.work_bytes, &p.work) != hipSuccess) {
-        (void)hipGetLastError();
-        p.work = nullptr;
-        set_error("bh_stitch_edge_shifts: %zu bytes of FFT work area", p.work_bytes);
-        return fail(BH_ERR_NOMEM);
-    }
-    for (hipfftHandle h : {p.r2c, p.c2r}) {
-        if ((p.work_bytes && hipfftSetWorkArea(h, p.work) != HIPFFT_SUCCESS) || hipfftSetStream(h, ctx->stream) != HIPFFT_SUCCESS) {
-            set_error("bh_stitch_edge_shifts: hipFFT plan set-up failed");
-            return fail(BH_ERR_HIP);
-        }
-    }
-    auto ins = ctx->plans.emplace(key, p);
-    *out = &ins.first->second;
-    return BH_OK;
+    const FftDesc d[2] = {fft_batched_2d(HIPFFT_D2Z, 2 * n_edges, n0, n1), fft_batched_2d(HIPFFT_Z2D, n_edges, n0, n1)};
+    return cached_plans(ctx, "bh_stitch_edge_shifts", FftKey{FftFamily::StripsF64, n_edges, n0, n1}, d, 2, out);
 }
 
 static GaussW gauss_weights() {  // scipy.ndimage._gaussian_kernel1d(sigma = 1.5, order 0, radius 6)
@@ -456,11 +415,11 @@ static int run_group(bh_ctx* ctx, const GroupBuffers& B, int relation, const std
 
     FftPlans* pl = nullptr;
     BH_TRY(get_strip_plans(ctx, n, g.n0, g.n1, &pl));
-    BH_CHECK_FFT(hipfftExecD2Z(pl->r2c, B.real, (hipfftDoubleComplex*)B.spec));
+    BH_CHECK_FFT(hipfftExecD2Z(pl->h[FFT_FWD], B.real, (hipfftDoubleComplex*)B.spec));
     const int64_t total = (int64_t)n * sper;
     const int egrid = (int)std::min<int64_t>(ceil_div(total, 256), (int64_t)ctx->num_cus * 16);
     hipLaunchKernelGGL(cross_power_kernel, dim3(egrid), dim3(256), 0, s, (const double2*)B.spec, B.R, sper, total, 1.0 / (double)per);
-    BH_CHECK_FFT(hipfftExecZ2D(pl->c2r, (hipfftDoubleComplex*)B.R, B.corr));
+    BH_CHECK_FFT(hipfftExecZ2D(pl->h[FFT_INV], (hipfftDoubleComplex*)B.R, B.corr));
 
     PeakGeom p{};
     p.n0 = g.n0, p.n1 = g.n1;
