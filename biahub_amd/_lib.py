@@ -24,7 +24,7 @@ FILTER_F32, FILTER_BF16 = 0, 1
 DS_STRIDE, DS_MEAN, DS_MIN, DS_MAX, DS_MEDIAN, DS_MODE = range(6)
 PSF_NCOL, PSF_NGUESS = 55, 22  # BH_PSF_NCOL, BH_PSF_NGUESS
 PSF_CONVERGED, PSF_ITERCAP, PSF_NONFINITE, PSF_SINGULAR, PSF_EMPTY = range(5)
-(T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD) = range(9)
+(T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_MOMENTS) = range(10)
 
 _i64, _f64, _f32, _int, _vp = C.c_int64, C.c_double, C.c_float, C.c_int, C.c_void_p
 
@@ -57,6 +57,8 @@ SIGNATURES = {
     "bh_focus_band_table": (_int, [_i64, _i64, _f64, _f64, _f64, _f64, _f64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_i64)]),
     "bh_focus_band_power": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _int, C.POINTER(_f64),
                                    C.POINTER(_f64)]),
+    "bh_volume_moments_plan": (_int, [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)]),
+    "bh_volume_moments": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _f64, _i64, _vp]),
     "bh_valid_mask": (_int, [_vp, _vp, _int, _i64, _vp, C.POINTER(C.c_uint64)]),
     "bh_bits_and": (_int, [_vp, _vp, _vp, _i64]),
     "bh_bits_unpack": (_int, [_vp, _vp, _i64, _vp]),

@@ -95,3 +95,17 @@ def flip_zyx(zyx_data: np.ndarray, x: bool = False, y: bool = False, device="cud
 def _check_nan_n_zeros(input_array: np.ndarray) -> bool:
     """True when the array is all zeros or all NaN (biahub/utils/array_ops.py:62-76); host-side."""
     return bool(np.all(np.isnan(input_array)) or np.all(input_array == 0))
+
+
+def get_empty_frame_indices(input_array, device="cuda") -> list[int]:
+    """Z indices of a 3-D array whose slice is entirely NaN or entirely zero (biahub/utils/array_ops.py:79-102), from one
+    ``volume_moments`` reduction: a numpy array or a device tensor; ``device="cpu"`` counts on the host."""
+    from .estimate_bleaching import volume_moments
+
+    if len(input_array.shape) != 3:
+        raise ValueError("Input array must be 3D.")
+    n = int(input_array.shape[1]) * int(input_array.shape[2])
+    if n == 0:  # np.all of nothing is True
+        return list(range(int(input_array.shape[0])))
+    rec =volume_moments(input_array, device)
+    return [z for z in range(len(rec)) if int(rec["n_nan"][z]) == n or int(rec["n_zero"][z]) == n]

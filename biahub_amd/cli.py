@@ -797,6 +797,33 @@ def characterize_psf_cli(input_position_dirpaths, config_filepath, output_dirpat
     characterize_psf(zyx_data, zyx_scale, settings, Path(output_dirpath), str(position), dataset_name, echo=click.echo)
 
 
+@cli.command("estimate-bleaching")
+@click.option("--input-position-dirpaths", "-i", multiple=True, required=True, callback=_positions)
+@click.option("--output-dirpath", "-o", required=True, type=click.Path(path_type=Path))
+def estimate_bleaching_cli(input_position_dirpaths, output_dirpath):
+    """Estimate bleaching from raw data: per position ``<out>/<row>/<col>/<fov>/bleaching.svg`` (reference: ``biahub
+    estimate-bleaching``, estimate_bleaching.py:105-154) plus ``bleaching.csv`` and ``bleaching_fit.csv``.  Every (t, c) volume is
+    reduced to its mean and standard deviation on the GPU; ``BH_BLEACHING_DEVICE=cpu`` reduces on the host with numpy instead.
+
+    >>> python -m biahub_amd estimate-bleaching -i ./input.zarr/0/0/0 -o ./bleaching-curves/
+    """
+    from .estimate_bleaching import estimate_bleaching_position, plate_zattrs
+
+    zattrs = plate_zattrs(input_position_dirpaths[0])
+    output_dirpath = Path(output_dirpath)
+    rank, world = parallel.init()
+    output_dirpath.mkdir(parents=True, exist_ok=True)
+    st = parallel.process_positions(list(input_position_dirpaths),
+                                    lambda p: estimate_bleaching_position(p, output_dirpath, zattrs, echo=click.echo), rank, world)
+    parallel.barrier()
+    rows = parallel.gather_stats(st)
+    failed = sum(r.n_failed for r in rows)
+    if st.n_failed:
+        raise click.ClickException(f"{st.n_failed} position(s) failed on rank {rank} (first: {st.first_error})")
+    if rank == 0 and failed:
+        raise click.ClickException(f"{failed} position(s) failed on other ranks")
+
+
 @cli.command("concatenate")
 @_config
 @click.option("--output-dirpath", "-o", required=True, type=click.Path(path_type=Path),

@@ -17,6 +17,9 @@
  *   bh_stitch_edge_shifts  <- biahub/vendor/stitch/tile.py:126-160 offset, _dexp_shim.py:139-182 register_translation_nd
  *   bh_focus_band_table, bh_focus_band_power
  *                          <- biahub/estimate_stabilization.py:948 focus_from_transverse_band (waveorder focus.compute_midband_power)
+ *   bh_volume_moments, bh_volume_moments_plan
+ *                          <- biahub/estimate_bleaching.py:42-46 plot_bleaching_curves (np.mean, np.std of every volume),
+ *                             biahub/utils/array_ops.py:79-102 get_empty_frame_indices
  *   bh_valid_mask, bh_bits_and, bh_bits_unpack
  *                          <- biahub/estimate_crop.py:58-94 estimate_crop_one_position (masks, counts, their AND)
  *   bh_blosc_unfilter, bh_blosc_filter
@@ -249,6 +252,42 @@ int bh_focus_band_table(int64_t Y, int64_t X, double pixel_size, double NA_det, 
 int bh_focus_band_power(bh_ctx* ctx, const void* window, int dtype, int64_t Z, int64_t Y, int64_t X, int64_t plane_stride,
                         int64_t row_stride, double pixel_size, double NA_det, double lambda_ill, double frac_lo, double frac_hi,
                         int max_batch, double* power, double* sum);
+
+/* ---- per-slice moments (estimate-bleaching's np.mean / np.std, biahub/estimate_bleaching.py:42-46; the empty-frame census of
+ * biahub/utils/array_ops.py:79-102) ---------------------------------------- */
+/* One record per z-slice, 64 bytes, every member 8 bytes wide:
+ *   n_nan, n_zero   voxels that are NaN (float32 only) / that compare equal to 0 (-0.0 counts)
+ *   min, max        over the voxels that are not NaN (+-inf take part); a slice without such a voxel has min = +inf, max = -inf
+ *   isum, isumsq    integer dtypes: sum of x in int64 and sum of x^2 in uint64, both EXACT; 0 for float32
+ *   fsum, fsumsq    float32: sum of (x - centre) and of (x - centre)^2, each term and each sum in float64; a NaN voxel makes
+ *                   both NaN, as np.mean does; 0 for the integer dtypes */
+typedef struct bh_moments {
+    uint64_t n_nan, n_zero;
+    double min, max;
+    int64_t isum;
+    uint64_t isumsq;
+    double fsum, fsumsq;
+} bh_moments;
+
+/* How a (Y, X) plane is cut into items: rows = consecutive rows per item (block_rows when > 0, clipped to Y; otherwise
+ * max(4, ceil(32768 / X)), clipped to Y), blocks = ceil(Y / rows) items per slice; wg_per_cu (may be NULL) = the cap of the
+ * reduction's grid in workgroups per compute unit: a volume of Z slices wraps the grid when Z * blocks exceeds
+ * wg_per_cu * compute units.  Host only.  BH_ERR_INVALID for a null pointer or an extent outside 1 .. 2^31 - 1. */
+int bh_volume_moments_plan(int64_t Y, int64_t X, int64_t block_rows, int64_t* rows, int64_t* blocks, int* wg_per_cu);
+
+/* out[z] (HOST, Z records) = the moments of slice z of the volume (Z, Y, X) that starts at `vol` (device, `dtype`: uint8, uint16,
+ * int16 or float32; only read): element (z, y, x) is vol[z * plane_stride + y * row_stride + x], strides in elements, so a view
+ * of a larger volume is read in place.  One pass over the bytes.  centre: float32 only (ignored otherwise); 0 gives the plain
+ * sums, the mean gives the corrected second moment of a two-pass variance.  The float64 sums are combined per item (slice, row
+ * block) and then per slice in a fixed order, without floating-point atomics: a repeated call on the same view returns the same
+ * bytes on any number of compute units (the order inside a row follows the row's offset from a 16-byte boundary).  LIMIT:
+ * Z * Y * X <= 2^32 voxels per call, which keeps the sum of squares of 16-bit data below 2^64; a larger volume is refused
+ * (split it along z).  block_rows <= 0: the plan's default.  Elapsed time: slot 9 of bh_last_elapsed_ms.  Synchronises once,
+ * before the records are read.  BH_ERR_INVALID before any device call for a null pointer, an unknown dtype, an extent < 1 or
+ * beyond 2^31 - 1, more than 2^32 voxels, row_stride < X, plane_stride < (Y - 1) * row_stride + X, an address that is no
+ * multiple of the element size, more than 2^31 - 1 items, and a centre that is not finite. */
+int bh_volume_moments(bh_ctx* ctx, const void* vol, int dtype, int64_t Z, int64_t Y, int64_t X, int64_t plane_stride, int64_t row_stride,
+                      double centre, int64_t block_rows, bh_moments* out);
 
 /* ---- validity masks (crop estimation, biahub/estimate_crop.py:58-94) -------------------- */
 /* bits: ceil(n / 64) * 2 words on the device; voxel i -> bit i % 32 of word i / 32, set when the voxel is neither 0 nor
@@ -601,7 +640,7 @@ int bh_crop_flip(bh_ctx* ctx, const void* in, int itemsize, int64_t C, int64_t Z
 /* ---- measurement support ----------------------------------------------------------- */
 /* Elapsed milliseconds of the last call of each kind, measured with HIP events on the
  * context's stream (what: 0 deskew kernel, 1 fill passes, 2 RL total, 3 tikhonov, 4 affine,
- * 5 crop_flip, 6 one RL iteration (mean), 7 transfer function, 8 flat field). Synchronises. */
+ * 5 crop_flip, 6 one RL iteration (mean), 7 transfer function, 8 flat field, 9 volume moments). Synchronises. */
 int bh_last_elapsed_ms(bh_ctx* ctx, int what, float* ms);
 /* Enable/disable event timing (off by default: events cost a few us per call). */
 int bh_ctx_set_timing(bh_ctx* ctx, int enabled);
