@@ -23,8 +23,9 @@ PCC_NORM = {None: 0, "magnitude": 1, "classic": 2}
 FILTER_F32, FILTER_BF16 = 0, 1
 DS_STRIDE, DS_MEAN, DS_MIN, DS_MAX, DS_MEDIAN, DS_MODE = range(6)
 PSF_NCOL, PSF_NGUESS = 55, 22  # BH_PSF_NCOL, BH_PSF_NGUESS
+GRAPH_KMAX = 16  # BH_GRAPH_KMAX
 PSF_CONVERGED, PSF_ITERCAP, PSF_NONFINITE, PSF_SINGULAR, PSF_EMPTY = range(5)
-(T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_MOMENTS) = range(10)
+(T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_MOMENTS, T_EDGECOST) = range(11)
 
 _i64, _f64, _f32, _int, _vp = C.c_int64, C.c_double, C.c_float, C.c_int, C.c_void_p
 
@@ -59,6 +60,8 @@ SIGNATURES = {
                                    C.POINTER(_f64)]),
     "bh_volume_moments_plan": (_int, [_i64, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)]),
     "bh_volume_moments": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _f64, _i64, _vp]),
+    "bh_edge_consistency_plan": (_int, [_i64, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int)]),
+    "bh_edge_consistency_cost": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _f32, _vp]),
     "bh_valid_mask": (_int, [_vp, _vp, _int, _i64, _vp, C.POINTER(C.c_uint64)]),
     "bh_bits_and": (_int, [_vp, _vp, _vp, _i64]),
     "bh_bits_unpack": (_int, [_vp, _vp, _i64, _vp]),

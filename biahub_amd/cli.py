@@ -602,17 +602,17 @@ def estimate_registration_cli(source_position_dirpaths, target_position_dirpaths
                               sbatch_filepath, local, registration_target_channel, registration_source_channel):
     """Estimate the source -> target transform and save it as ``register`` / ``stabilize`` settings
     (reference: ``biahub estimate-registration``, estimate_registration.py:358-536).  ``estimation_method: ants``
-    runs on the GPU (Mattes-MI similarity estimate); ``manual`` (napari) and ``beads`` are not part of this package."""
-    from .registration.ants import estimate_tczyx
+    (Mattes-MI similarity estimate) and ``beads`` (bead detection, graph matching, point-set fit: registration/beads.py) run on the
+    GPU; ``manual`` (napari) is not part of this package."""
 
     output_filepath = Path(output_filepath)
     output_dir = output_filepath.parent
     output_dir.mkdir(parents=True, exist_ok=True)
     settings = yaml_to_model(config_filepath, EstimateRegistrationSettings)
     click.echo(f"Settings: {settings}")
-    if settings.estimation_method != "ants":
+    if settings.estimation_method not in ("ants", "beads"):
         raise click.UsageError(f"estimation_method {settings.estimation_method!r} is not available in biahub_amd "
-                               "(only 'ants'); use the reference biahub package for 'manual' and 'beads'.")
+                               "(only 'ants' and 'beads'); use the reference biahub package for 'manual'.")
     target_channel_name, source_channel_name = settings.target_channel_name, settings.source_channel_name
     reg_target = registration_target_channel or target_channel_name
     reg_sources = list(registration_source_channel) or [source_channel_name]
@@ -622,17 +622,33 @@ def estimate_registration_cli(source_position_dirpaths, target_position_dirpaths
         source_channel_index = src.channel_names.index(source_channel_name)
         target_channel_index = tgt.channel_names.index(target_channel_name)
         voxel_size = list(tgt.scale)
-        transforms = estimate_tczyx(
-            mov_tczyx=src.data, ref_tczyx=tgt.data, mov_channel_index=source_channel_index,
-            ref_channel_index=target_channel_index, ants_registration_settings=settings.ants_registration_settings,
-            affine_transform_settings=settings.affine_transform_settings, verbose=settings.verbose,
-            output_folder_path=output_dir, cluster="local", sbatch_filepath=sbatch_filepath)
+        if settings.estimation_method == "beads":
+            from .registration.beads import estimate_tczyx
+
+            transforms = estimate_tczyx(
+                mov_tczyx=src.data, ref_tczyx=tgt.data, mov_channel_index=source_channel_index,
+                ref_channel_index=target_channel_index, beads_match_settings=settings.beads_match_settings,
+                affine_transform_settings=settings.affine_transform_settings, verbose=settings.verbose, cluster="local",
+                sbatch_filepath=sbatch_filepath, output_folder_path=output_dir, ref_voxel_size=tuple(tgt.scale[-3:]),
+                mov_voxel_size=tuple(src.scale[-3:]))
+            missing = [t for t, m in enumerate(transforms) if m is None]
+            if missing:  # the reference hands these to evaluate_transforms (eval_transform_settings), which is not part of this package
+                raise click.UsageError(f"no transform could be estimated for timepoint(s) {missing} (empty data); "
+                                       "interpolating over them (eval_transform_settings) is not available in biahub_amd")
+        else:
+            from .registration.ants import estimate_tczyx
+
+            transforms = estimate_tczyx(
+                mov_tczyx=src.data, ref_tczyx=tgt.data, mov_channel_index=source_channel_index,
+                ref_channel_index=target_channel_index, ants_registration_settings=settings.ants_registration_settings,
+                affine_transform_settings=settings.affine_transform_settings, verbose=settings.verbose,
+                output_folder_path=output_dir, cluster="local", sbatch_filepath=sbatch_filepath)
     if len(transforms) == 1:
         model = RegistrationSettings(source_channel_names=reg_sources, target_channel_name=reg_target,
                                      affine_transform_zyx=transforms[0])
     else:
         model = StabilizationSettings(stabilization_estimation_channel=target_channel_name, stabilization_type="affine",
-                                      stabilization_method="ants",
+                                      stabilization_method=settings.estimation_method,
                                       stabilization_channels=[source_channel_name, target_channel_name],
                                       affine_transform_zyx_list=transforms, time_indices="all",
                                       output_voxel_size=voxel_size)
@@ -687,10 +703,12 @@ def optimize_registration_cli(source_position_dirpaths, target_position_dirpaths
 @click.option("--local", "-l", is_flag=True, default=False)
 def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_filepath, sbatch_filepath, local):
     """Estimate per-timepoint stabilization transforms (reference: ``biahub estimate-stabilization``,
-    estimate_stabilization.py:1223-1640).  Two combinations run here: ``stabilization_type: xyz`` with ``stabilization_method:
-    phase-cross-corr`` (GPU phase cross-correlation; ``xyz_stabilization_settings/<fov>.yml``) and ``stabilization_type: z`` with
-    the reference's default ``focus-finding`` (GPU mid-band power; ``z_stabilization_settings/<fov>.yml``, or ``average.yml``
-    with ``average_across_wells``).  Each file feeds ``stabilize``."""
+    estimate_stabilization.py:1223-1640).  Three combinations run here: ``stabilization_type: xyz`` with ``stabilization_method:
+    phase-cross-corr`` (GPU phase cross-correlation; ``xyz_stabilization_settings/<fov>.yml``), ``xyz`` with ``beads`` (bead
+    matching of the first position's estimation channel against its first or neighbouring timepoint, registration/beads.py;
+    ``xyz_stabilization_settings.yml``) and ``stabilization_type: z`` with the reference's default ``focus-finding`` (GPU mid-band
+    power; ``z_stabilization_settings/<fov>.yml``, or ``average.yml`` with ``average_across_wells``).  Each file feeds
+    ``stabilize``."""
     from .estimate_stabilization import estimate_xyz_stabilization_pcc, estimate_z_stabilization, save_transforms
 
     settings = yaml_to_model(config_filepath, EstimateStabilizationSettings)
@@ -700,10 +718,10 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
         raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method 'focus-finding' registers xy with "
                                "StackReg (pystackreg), which is not available in biahub_amd; 'focus-finding' runs here with "
                                "stabilization_type 'z', and 'xyz' with 'phase-cross-corr'.")
-    if combo not in (("xyz", "phase-cross-corr"), ("z", "focus-finding")):
+    if combo not in (("xyz", "phase-cross-corr"), ("xyz", "beads"), ("z", "focus-finding")):
         raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method "
                                f"{settings.stabilization_method!r} is not available in biahub_amd (only 'xyz' with "
-                               "'phase-cross-corr' and 'z' with 'focus-finding'); use the reference biahub package for beads.")
+                               "'phase-cross-corr' or 'beads' and 'z' with 'focus-finding').")
     if settings.eval_transform_settings:
         raise click.UsageError("eval_transform_settings (transform validation / interpolation) is not available in biahub_amd")
     output_dirpath = Path(output_dirpath)
@@ -720,6 +738,32 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
             centre_window(*fov_yx, focus_settings.center_crop_xy)
         except ValueError as e:
             raise click.UsageError(str(e)) from None
+    if combo == ("xyz", "beads"):
+        from .registration.beads import estimate_tczyx
+
+        click.echo("Estimating xyz stabilization parameters with beads")
+        with open_ome_zarr(input_position_dirpaths[0]) as ds:
+            transforms = estimate_tczyx(mov_tczyx=ds.data, ref_tczyx=ds.data, mov_channel_index=channel_index,
+                                        ref_channel_index=channel_index, beads_match_settings=settings.beads_match_settings,
+                                        affine_transform_settings=settings.affine_transform_settings, verbose=settings.verbose,
+                                        output_folder_path=output_dirpath, mode="stabilization", cluster="local",
+                                        sbatch_filepath=sbatch_filepath)
+        if transforms and transforms[0] is None:  # with propagation timepoint 0 is not estimated: it is its own reference
+            transforms[0] = np.eye(4).tolist()
+        missing = [t for t, m in enumerate(transforms) if m is None]
+        if missing:  # the reference hands these to evaluate_transforms (eval_transform_settings), refused above
+            raise click.UsageError(f"no transform could be estimated for timepoint(s) {missing} (empty data); "
+                                   "interpolating over them (eval_transform_settings) is not available in biahub_amd")
+        if parallel.world_info()[0] == 0:
+            model = StabilizationSettings(stabilization_type=settings.stabilization_type,
+                                          stabilization_method=settings.stabilization_method,
+                                          stabilization_estimation_channel=settings.stabilization_estimation_channel,
+                                          stabilization_channels=settings.stabilization_channels,
+                                          affine_transform_zyx_list=[np.eye(4).tolist()], time_indices="all",
+                                          output_voxel_size=voxel_size)
+            save_transforms(model, transforms, output_dirpath / "xyz_stabilization_settings.yml")
+        click.echo(f"Stabilization settings saved to {output_dirpath.resolve()}")
+        return
     if combo == ("xyz", "phase-cross-corr"):
         click.echo("Estimating xyz stabilization parameters with phase cross correlation")
         pcc = settings.phase_cross_corr_settings or PhaseCrossCorrSettings()

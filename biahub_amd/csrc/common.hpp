@@ -52,7 +52,7 @@ void set_error(const char* fmt, ...);
         if (_s != BH_OK) return _s;  \
     } while (0)
 
-enum TimerSlot { T_DESKEW = 0, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_MOMENTS, T_COUNT };
+enum TimerSlot { T_DESKEW = 0, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_MOMENTS, T_EDGECOST, T_COUNT };
 
 // One hipFFT plan.  `volume`: the 3-D real transform of (n[0], n[1], n[2]) through hipfftMakePlan3d (the entry point the
 // self-check of get_plans exists for), `type` R2C or C2R.  Otherwise one hipfftMakePlanMany call, the members in the order of

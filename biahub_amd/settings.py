@@ -10,7 +10,7 @@ from __future__ import annotations
 from typing import Literal
 
 import numpy as np
-from pydantic import (BaseModel, ConfigDict, NonNegativeFloat, NonNegativeInt, PositiveFloat, PositiveInt, field_validator,
+from pydantic import (BaseModel, ConfigDict, Field, NonNegativeFloat, NonNegativeInt, PositiveFloat, PositiveInt, field_validator,
                       model_validator)
 
 OmeZarrVersion = Literal["0.4", "0.5"]
@@ -144,14 +144,100 @@ class AntsRegistrationSettings(_Strict):
     clip: bool = False
 
 
+class DetectPeaksSettings(_Strict):
+    """biahub/settings.py:26-30: what ``detect_peaks`` is called with on one side of a bead registration."""
+
+    threshold_abs: float = 110
+    nms_distance: int = 16
+    min_distance: int = 0
+    block_size: list[int] = [8, 8, 8]
+
+
+class EdgeGraphSettings(BaseModel):
+    """biahub/settings.py:130-148 (extra keys are not rejected there either): the parameter of the chosen method gets its
+    default, the other one is cleared."""
+
+    method: Literal["knn", "radius", "full"] = "knn"
+    k: int | None = None
+    radius: float | None = None
+
+    @model_validator(mode="after")
+    def _per_method(self):
+        if self.method == "knn":
+            self.k = 5 if self.k is None else self.k
+            self.radius = None
+        elif self.method == "radius":
+            self.radius = 30.0 if self.radius is None else self.radius
+            self.k = None
+        else:
+            self.k = self.radius = None
+        return self
+
+
+class CostMatrixSettings(_Strict):
+    """biahub/settings.py:151-160."""
+
+    weights: dict[str, float] = {"dist": 0.5, "edge_angle": 1.0, "edge_length": 1.0, "pca_dir": 0.0, "pca_aniso": 0.0,
+                                 "edge_descriptor": 0.0}
+    normalize: bool = False
+
+
+class HungarianMatchSettings(_Strict):
+    """biahub/settings.py:163-169."""
+
+    distance_metric: Literal["euclidean", "cosine", "cityblock"] = "euclidean"
+    cost_threshold: float = 0.10
+    max_ratio: float = 0.8
+    cross_check: bool = False
+    edge_graph_settings: EdgeGraphSettings = EdgeGraphSettings()
+    cost_matrix_settings: CostMatrixSettings = CostMatrixSettings()
+
+
+class MatchDescriptorSettings(_Strict):
+    """biahub/settings.py:172-175 (carried for the YAML surface: ``algorithm: match_descriptor`` is refused where it is used)."""
+
+    distance_metric: Literal["euclidean", "cosine", "cityblock"] = "euclidean"
+    max_ratio: float = 0.8
+    cross_check: bool = False
+
+
+class FilterMatchesSettings(_Strict):
+    """biahub/settings.py:178-182."""
+
+    angle_threshold: float = 0
+    direction_threshold: float = 0
+    min_distance_quantile: float = 0.01
+    max_distance_quantile: float = 0.95
+
+
+class QCBeadsRegistrationSettings(_Strict):
+    """biahub/settings.py:185-188."""
+
+    iterations: int = 2
+    score_threshold: float = 0.40
+    score_centroid_mask_radius: int = 6
+
+
+class BeadsMatchSettings(_Strict):
+    """biahub/settings.py:191-202."""
+
+    algorithm: Literal["hungarian", "match_descriptor"] = "hungarian"
+    source_peaks_settings: DetectPeaksSettings | None = Field(default_factory=DetectPeaksSettings)
+    target_peaks_settings: DetectPeaksSettings | None = Field(default_factory=DetectPeaksSettings)
+    match_descriptor_settings: MatchDescriptorSettings = MatchDescriptorSettings()
+    hungarian_match_settings: HungarianMatchSettings = HungarianMatchSettings()
+    filter_matches_settings: FilterMatchesSettings = FilterMatchesSettings()
+    qc_settings: QCBeadsRegistrationSettings = QCBeadsRegistrationSettings()
+
+
 class EstimateRegistrationSettings(_Strict):
-    """biahub/settings.py:270-292; only ``estimation_method: ants`` runs here (manual needs napari, beads is a CPU
-    point-matching flow: SURVEY.md §8f), the other methods' sub-settings are carried through untouched."""
+    """biahub/settings.py:270-292; ``estimation_method: ants`` and ``beads`` run here (manual needs napari), the sub-settings of
+    the methods that do not are carried through untouched."""
 
     target_channel_name: str
     source_channel_name: str
     estimation_method: Literal["manual", "beads", "ants"] = "manual"
-    beads_match_settings: dict | None = None
+    beads_match_settings: BeadsMatchSettings | None = None
     focus_finding_settings: dict | None = None
     affine_transform_settings: AffineTransformSettings = AffineTransformSettings()
     eval_transform_settings: dict | None = None
@@ -163,6 +249,8 @@ class EstimateRegistrationSettings(_Strict):
     def _defaults(self):
         if self.estimation_method == "ants" and self.ants_registration_settings is None:
             self.ants_registration_settings = AntsRegistrationSettings()
+        if self.estimation_method == "beads" and self.beads_match_settings is None:
+            self.beads_match_settings = BeadsMatchSettings()
         return self
 
 
@@ -217,21 +305,27 @@ class FocusFindingSettings(_Strict):
 
 
 class EstimateStabilizationSettings(_Strict):
-    """biahub/settings.py:295-310; ``phase-cross-corr`` (xyz) and ``focus-finding`` (z) run in this package.  The sub-settings
-    of the other methods are carried as plain dicts, and so is ``focus_finding_settings``, which is validated into
+    """biahub/settings.py:295-333; ``phase-cross-corr`` (xyz), ``beads`` (xyz) and ``focus-finding`` (z) run in this package.
+    ``stack_reg_settings`` is carried as a plain dict, and so is ``focus_finding_settings``, which is validated into
     ``FocusFindingSettings`` where it is used."""
 
     stabilization_estimation_channel: str
     stabilization_channels: list
     stabilization_type: Literal["z", "xy", "xyz"]
     stabilization_method: Literal["beads", "phase-cross-corr", "focus-finding"] = "focus-finding"
-    beads_match_settings: dict | None = None
+    beads_match_settings: BeadsMatchSettings | None = None
     phase_cross_corr_settings: PhaseCrossCorrSettings | None = None
     stack_reg_settings: dict | None = None
     focus_finding_settings: dict | None = None
     affine_transform_settings: AffineTransformSettings = AffineTransformSettings()
     eval_transform_settings: dict | None = None
     verbose: bool = False
+
+    @model_validator(mode="after")
+    def _defaults(self):
+        if self.stabilization_method == "beads" and self.beads_match_settings is None:
+            self.beads_match_settings = BeadsMatchSettings()
+        return self
 
 
 class DeconvolveSettings(_Strict):

@@ -20,6 +20,9 @@
  *   bh_volume_moments, bh_volume_moments_plan
  *                          <- biahub/estimate_bleaching.py:42-46 plot_bleaching_curves (np.mean, np.std of every volume),
  *                             biahub/utils/array_ops.py:79-102 get_empty_frame_indices
+ *   bh_edge_consistency_cost, bh_edge_consistency_plan
+ *                          <- biahub/core/graph_matching.py:518-571 GraphMatcher._compute_edge_consistency_cost (the n x m
+ *                             small assignment problems of bead matching, biahub/registration/beads.py)
  *   bh_valid_mask, bh_bits_and, bh_bits_unpack
  *                          <- biahub/estimate_crop.py:58-94 estimate_crop_one_position (masks, counts, their AND)
  *   bh_blosc_unfilter, bh_blosc_filter
@@ -288,6 +291,28 @@ int bh_volume_moments_plan(int64_t Y, int64_t X, int64_t block_rows, int64_t* ro
  * multiple of the element size, more than 2^31 - 1 items, and a centre that is not finite. */
 int bh_volume_moments(bh_ctx* ctx, const void* vol, int dtype, int64_t Z, int64_t Y, int64_t X, int64_t plane_stride, int64_t row_stride,
                       double centre, int64_t block_rows, bh_moments* out);
+
+/* ---- bead graph matching: the edge-consistency cost matrix (biahub/core/graph_matching.py:518-571) -------- */
+#define BH_GRAPH_KMAX 16 /* most edge attributes per node */
+/* How the n x m pairs are cut into tiles of tile_n x tile_m pairs, one workgroup per tile at a time: tiles = ceil(n / tile_n) *
+ * ceil(m / tile_m); wg_per_cu (may be NULL) = the cap of the grid in workgroups per compute unit: a matrix wraps the grid
+ * when tiles exceeds wg_per_cu * compute units.  Host only.  BH_ERR_INVALID for a null pointer or n, m outside 0 .. 2^31 - 1. */
+int bh_edge_consistency_plan(int64_t n, int64_t m, int64_t* tile_n, int64_t* tile_m, int64_t* tiles, int* wg_per_cu);
+
+/* cost[i * m + j] (device, n x m float32) for the nodes i of one graph and j of another.  attr_a: n x kmax float32 (device), row i
+ * holding the cnt_a[i] (device, int32; clamped to 0 .. kmax) attributes of node i's edges in any order, the rest of the row
+ * ignored; attr_b, cnt_b, m: the same for the other graph; 1 <= kmax <= BH_GRAPH_KMAX.  Neither input is written.
+ *   cnt_a[i] == 0 or cnt_b[j] == 0:  default_cost
+ *   otherwise:  the minimum, over the assignments of min(k_i, k_j) pairs, of the sum of the entries C[p][q] =
+ *               float32(|double(a_p) - double(b_q)|), summed and divided by the number of pairs in float64, rounded once:
+ *               what scipy's linear_sum_assignment followed by the mean of the matched entries returns, up to the
+ *               reference's float32 summation.  Found without a general solver: on sorted rows an optimal matching of
+ *               |a - b| never crosses (equal counts pair in order, unequal ones take a monotone dynamic programme).
+ * One writer per element and no atomics: repeated calls return the same bytes.  Enqueued on the context's stream, does not
+ * synchronise.  Elapsed time: slot 10 of bh_last_elapsed_ms.  n == 0 or m == 0 does nothing.  BH_ERR_INVALID before any device
+ * call for a null pointer, kmax outside 1 .. BH_GRAPH_KMAX, n or m outside 0 .. 2^31 - 1. */
+int bh_edge_consistency_cost(bh_ctx* ctx, const float* attr_a, const int32_t* cnt_a, int64_t n, const float* attr_b,
+                             const int32_t* cnt_b, int64_t m, int kmax, float default_cost, float* cost);
 
 /* ---- validity masks (crop estimation, biahub/estimate_crop.py:58-94) -------------------- */
 /* bits: ceil(n / 64) * 2 words on the device; voxel i -> bit i % 32 of word i / 32, set when the voxel is neither 0 nor
@@ -640,7 +665,8 @@ int bh_crop_flip(bh_ctx* ctx, const void* in, int itemsize, int64_t C, int64_t Z
 /* ---- measurement support ----------------------------------------------------------- */
 /* Elapsed milliseconds of the last call of each kind, measured with HIP events on the
  * context's stream (what: 0 deskew kernel, 1 fill passes, 2 RL total, 3 tikhonov, 4 affine,
- * 5 crop_flip, 6 one RL iteration (mean), 7 transfer function, 8 flat field, 9 volume moments). Synchronises. */
+ * 5 crop_flip, 6 one RL iteration (mean), 7 transfer function, 8 flat field, 9 volume moments,
+ * 10 edge-consistency cost). Synchronises. */
 int bh_last_elapsed_ms(bh_ctx* ctx, int what, float* ms);
 /* Enable/disable event timing (off by default: events cost a few us per call). */
 int bh_ctx_set_timing(bh_ctx* ctx, int enabled);
