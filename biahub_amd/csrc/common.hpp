@@ -138,6 +138,7 @@ int free_scratch(bh_ctx* ctx, const char* name);
 // the workspace's allocator (hipMalloc, or the virtual-memory API under BH_ALLOC_VMM_MB: context.hip)
 hipError_t dev_alloc(int device, size_t bytes, void** out);
 hipError_t dev_free(void* p);
+hipError_t dev_alloc_variant(int device, size_t bytes, size_t chunk_bytes, long long seed, void** out);  // survey blocks
 bool dev_alloc_is_shuffled();  // the default layout is in force (not switched off by BH_ALLOC_VMM_MB=0)
 bool dev_block_is_vmm(const void* p);  // this block was built from mapped chunks (large enough for the layout)
 // The set cached under `key`, or built from the n (1 to 3) descriptions and inserted.  All or nothing: on failure nothing is

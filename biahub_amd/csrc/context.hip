@@ -71,7 +71,8 @@ static hipError_t vmm_unmap_all(void* va, const VmmBlock& blk, size_t mapped_chu
 static std::mutex g_vmm_mu;
 static std::map<void*, VmmBlock> g_vmm;
 
-static hipError_t vmm_alloc(int device, size_t bytes, size_t chunk, bool shuffle, void** out) {
+// seed >= 0: that permutation for this block (dev_alloc_variant); < 0: the counter, or BH_ALLOC_VMM_SEED
+static hipError_t vmm_alloc(int device, size_t bytes, size_t chunk, bool shuffle, void** out, long long seed = -1) {
     hipMemAllocationProp prop = {};
     prop.type = hipMemAllocationTypePinned;
     prop.location.type = hipMemLocationTypeDevice;
@@ -101,7 +102,7 @@ static hipError_t vmm_alloc(int device, size_t bytes, size_t chunk, bool shuffle
         static std::atomic<unsigned long long> counter{0};
         static const char* seed_env = getenv("BH_ALLOC_VMM_SEED");  // an integer: that permutation for every allocation
         unsigned long long st = 0x9E3779B97F4A7C15ull +
-                                0xD1B54A32D192ED03ull * (seed_env ? strtoull(seed_env, nullptr, 10) : counter.fetch_add(1) + 1);
+                                0xD1B54A32D192ED03ull * (seed >= 0 ? (unsigned long long)seed : seed_env ? strtoull(seed_env, nullptr, 10) : counter.fetch_add(1) + 1);
         for (size_t i = n - 1; i > 0; --i) {
             st = st * 6364136223846793005ull + 1442695040888963407ull;
             std::swap(slot[i], slot[(size_t)((st >> 33) % (i + 1))]);
@@ -191,6 +192,11 @@ static hipError_t dev_alloc_raw(int device, size_t bytes, void** out) {
         g_vmm_failed.store(true);
     }
     return hipMalloc(out, bytes);
+}
+// A gigabyte block with a chunk size and a permutation seed of the caller's choosing, whatever the process-wide switches say:
+// the survey of fftconv_tune_spectrum (BH_FC_TUNE_SURVEY=1) compares such blocks.  Freed by dev_free like any other.
+hipError_t dev_alloc_variant(int device, size_t bytes, size_t chunk_bytes, long long seed, void** out) {
+    return vmm_alloc(device, bytes, chunk_bytes, true, out, seed);
 }
 hipError_t dev_free(void* p) {
     if (!p) return hipSuccess;

@@ -518,7 +518,7 @@ static int rl_engine_run(bh_ctx* ctx, ConvPlan* pl, const float* d, const void* 
         Scratch& sc = ctx->scratch["fc_spec"];
         // the audition may free the allocation it was handed and keep another one: the scratch table must follow it on the
         // error path too, or the next get_scratch("fc_spec") hands out a freed pointer
-        const int tune_rc = fftconv_tune_spectrum(ctx, *pl, out, sc.bytes, &spec);
+        const int tune_rc = fftconv_tune_spectrum(ctx, *pl, reinterpret_cast<const cf*>(otf), otf_real, zr, zreal, out, sc.bytes, &spec);
         sc.ptr = spec;
         ctx->spec_tuned = spec;
         BH_TRY(tune_rc);

@@ -23,7 +23,9 @@
 // with its launcher (fftconv_col.hip, fftconv_xtile.hip, fftconv_xw.hip, fftconv_colreg.hip); fftconv_dev.hpp is what they
 // share, fftconv.hpp what the rest of the library sees.
 #include "fftconv_dev.hpp"
+#include "tune_rule.hpp"
 
+#include <chrono>
 #include <mutex>
 
 namespace bh {
@@ -435,62 +437,135 @@ int fftconv_richardson_lucy(bh_ctx* ctx, const ConvPlan& pl, const float* d, con
     return BH_OK;
 }
 
-// Where the driver puts the spectrum matters to ONE kernel: the fused update X pass (S read and written, the estimate read and
-// written: four streams) takes 6.0 to 7.1 ms depending on the physical pages behind `spec` — the same virtual address
-// re-allocated gives 35.0 to 36.2 ms per iteration at config 2, offsets inside one allocation give the same time to
-// +-0.05 ms, every other kernel is indifferent (tools/ctx_probe.py).  So a new spectrum allocation of a large
-// volume is auditioned once: the pass is timed on it and on up to four more allocations held at the same time, until a fast and a
-// slow one have both been seen, and the fastest stays (30-70 ms and up to 35 GB of transient memory once per context and shape;
-// BH_FC_TUNE_ALLOC=0 skips it).
-// `est` is any V-float buffer the caller is about to overwrite (the pass reads and writes it), `bytes` the allocation size.
-int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, float* est, size_t bytes, cf** spec) {
+// Where the driver puts the spectrum matters to the passes that stream it.  A process's R-L iteration lands on one of two levels
+// (profiles/zdirect_real_taps_ab.txt, r04ai_box_state_ab.txt: Y pass 2.99 or 3.50 ms, Z +8 %, the X passes +8-11 %), and most of
+// the difference sits in the passes that touch nothing but the spectrum.  So a new spectrum allocation is auditioned once: the
+// launches that touch only the candidate (Y forward, the Z pass of the plan, Y inverse) run twice on the zero-filled block, the
+// second repetition is its time, and further candidates are drawn and HELD AT THE SAME TIME (so that the driver hands out other
+// physical chunks) until the rule of tune_rule.hpp says stop; the fastest stays, the others are freed.  What profiles/
+// spectrum_audition.txt measured of it (levels, share of slow draws, cost) is in DESIGN.md 2.
+//   BH_FC_TUNE_ALLOC=0 / 1   never / always audition (the default is kTuneDefaultOn below)
+//   BH_FC_TUNE_MIN_VOXELS=n  smallest volume that is auditioned (default 2^28: below it the passes run out of the caches)
+//   BH_DEBUG_SCRATCH=1       one "[bh tune]" line per audition: every candidate's time and the choice
+//   BH_FC_TUNE_SURVEY=1      measurement only: no early stop, the fused update X pass timed as well (it reads and writes `est`),
+//                            every launch printed per candidate, and three more blocks that are never kept: two with the same
+//                            permutation seed (they differ in their physical chunks only) and one of 16-MiB chunks
+// A candidate is drawn only while free memory after it stays at least twice its size (the result and the deskew output are
+// still to be allocated in the same step).  A failed allocation ends the draws with its error cleared; a failed probe ends
+// them and is returned, after the best candidate so far took the block's place.
+// `est` is any V-float buffer the caller is about to overwrite, `bytes` the allocation size, `otf` ... `zreal` what the
+// iteration's Z pass will be launched with.
+constexpr int kTuneDefaultOn = 1;
+int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, const cf* otf, bool otf_real, int zr, bool zreal, float* est, size_t bytes,
+                          cf** spec) {
     const double V = (double)pl.d.Z * pl.d.Y * pl.d.X;
-    // Round 3: with the workspace's default layout (2-MiB physical chunks in a shuffled order, context.hip dev_alloc) the pass
-    // reads 5.87-6.5 ms on every allocation tried and the audition is off; it stays for the hipMalloc layout
-    // (BH_ALLOC_VMM_MB=0), where the two states are 5.95 and 7.07 ms.  BH_FC_TUNE_ALLOC=0 / 1 forces it off / on.
-    const bool tune = env_int("BH_FC_TUNE_ALLOC", !(dev_alloc_is_shuffled() && dev_block_is_vmm(*spec))) != 0;
-    if (!pl.xw || V < (double)(1u << 28) || !tune) return BH_OK;
-    hipEvent_t e0, e1;
-    BH_CHECK_HIP(hipEventCreate(&e0));
-    BH_CHECK_HIP(hipEventCreate(&e1));
-    auto audition = [&](cf* s, float* ms) -> int {
-        for (int rep = 0; rep < 2; ++rep) {  // the second launch is the measurement
-            BH_CHECK_HIP(hipEventRecord(e0, ctx->stream));
-            BH_TRY(launch_x(ctx, pl, true, XE_UPDATE, nullptr, s, est, est, 1e-6f, true));
-            BH_CHECK_HIP(hipEventRecord(e1, ctx->stream));
-            BH_CHECK_HIP(hipEventSynchronize(e1));
-            BH_CHECK_HIP(hipEventElapsedTime(ms, e0, e1));
+    const char* min_env = getenv("BH_FC_TUNE_MIN_VOXELS");
+    const double min_voxels = min_env ? atof(min_env) : (double)(1u << 28);
+    const bool survey = env_int("BH_FC_TUNE_SURVEY", 0) != 0;
+    // pl.xw: every shape the audition was measured on runs the wave-private X passes
+    if (!pl.xw || V < min_voxels || env_int("BH_FC_TUNE_ALLOC", kTuneDefaultOn) == 0) return BH_OK;
+    struct Events {
+        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t ev : e)
+                if (ev) (void)hipEventDestroy(ev);
+        }
+    } ev;
+    for (hipEvent_t& e : ev.e) BH_CHECK_HIP(hipEventCreate(&e));
+    struct Probe {
+        float t[4] = {0.f, 0.f, 0.f, 0.f};  // Y forward, Z, Y inverse, fused update X (survey only)
+        float ms() const { return t[0] + t[1] + t[2]; }
+    };
+    hipStream_t st = ctx->stream;
+    auto probe = [&](cf* s, Probe* p) -> int {
+        BH_CHECK_HIP(hipMemsetAsync(s, 0, bytes, st));
+        for (int rep = 0; rep < 2; ++rep) {  // the second repetition is the measurement
+            BH_CHECK_HIP(hipEventRecord(ev.e[0], st));
+            BH_TRY(launch_col(ctx, pl, COL_FWD, false, s, nullptr, 1.f));
+            BH_CHECK_HIP(hipEventRecord(ev.e[1], st));
+            BH_TRY(launch_rl_z(ctx, pl, false, otf_real, zr, zreal, s, otf));
+            BH_CHECK_HIP(hipEventRecord(ev.e[2], st));
+            BH_TRY(launch_col(ctx, pl, COL_INV, false, s, nullptr, 1.f));
+            BH_CHECK_HIP(hipEventRecord(ev.e[3], st));
+            if (survey) BH_TRY(launch_x(ctx, pl, true, XE_UPDATE, nullptr, s, est, est, 1e-6f, true));
+            BH_CHECK_HIP(hipEventRecord(ev.e[4], st));
+            BH_CHECK_HIP(hipEventSynchronize(ev.e[4]));
+            for (int k = 0; k < 4; ++k) BH_CHECK_HIP(hipEventElapsedTime(&p->t[k], ev.e[k], ev.e[k + 1]));
         }
         return BH_OK;
     };
-    constexpr int NC = 5;  // four of six simultaneous allocations measured slow: five tries leave ~13 % of the draws without a fast one
-    cf* cand[NC] = {*spec, nullptr, nullptr, nullptr, nullptr};
-    float ms[NC] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int n = 1, best = 0, rc = audition(cand[0], &ms[0]);
-    float slowest = ms[0];
-    for (; rc == BH_OK && n < NC; ++n) {
-        if (ms[best] < 0.93f * slowest) break;  // both levels seen: the fast one is in hand
-        if (dev_alloc(ctx->device, bytes, (void**)&cand[n]) != hipSuccess) {
+    auto room_for_one_more = [&]() {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
             (void)hipGetLastError();
-            cand[n] = nullptr;
-            break;
+            return false;
         }
-        rc = audition(cand[n], &ms[n]);
-        if (rc != BH_OK) {
-            ++n;
-            break;
+        return free_b >= 3 * bytes;
+    };
+    const auto t_begin = std::chrono::steady_clock::now();
+    TuneRule rule = kTuneRuleDefault;
+    if (survey) rule = {6, 0.f};  // six candidates, and no second level is ever "seen": all of them are drawn
+    constexpr int NC = 16;
+    if (rule.max_candidates > NC) rule.max_candidates = NC;
+    cf* cand[NC] = {*spec};
+    float ms[NC] = {0.f};
+    Probe pr[NC];
+    int n = 0, rc = BH_OK;
+    TuneDecision dec = {false, 0};
+    while (!dec.stop) {
+        if (n > 0) {  // candidate 0 is the allocation the caller came with
+            if (!room_for_one_more()) break;
+            if (dev_alloc(ctx->device, bytes, (void**)&cand[n]) != hipSuccess) {
+                (void)hipGetLastError();
+                cand[n] = nullptr;
+                ms[n++] = 0.f;  // a candidate without a time: the rule stops on it
+                dec = tune_decide(rule, ms, n);
+                break;
+            }
         }
-        if (ms[n] < ms[best]) best = n;
-        if (ms[n] > slowest) slowest = ms[n];
+        rc = probe(cand[n], &pr[n]);
+        ms[n] = rc == BH_OK ? pr[n].ms() : 0.f;
+        ++n;
+        dec = tune_decide(rule, ms, n);
+        if (rc != BH_OK) break;
     }
-    if (getenv("BH_DEBUG_SCRATCH"))
-        fprintf(stderr, "[bh tune] fused update pass on %d spectrum allocation(s): %.3f %.3f %.3f %.3f %.3f ms -> #%d\n", n, ms[0], ms[1],
-                ms[2], ms[3], ms[4], best);
+    const bool debug = getenv("BH_DEBUG_SCRATCH") != nullptr;
+    if (survey && debug && rc == BH_OK) {
+        for (int i = 0; i < n; ++i)
+            if (cand[i])
+                fprintf(stderr, "[bh tune survey] #%d Y fwd %.3f  Z %.3f  Y inv %.3f  update X %.3f ms  (%s)\n", i, pr[i].t[0], pr[i].t[1],
+                        pr[i].t[2], pr[i].t[3], i ? "drawn" : "the caller's");
+        if (dev_block_is_vmm(cand[0])) {
+            const struct { size_t chunk; const char* what; } extra[3] = {{(size_t)2 << 20, "2-MiB chunks, seed 12345"},
+                                                                          {(size_t)2 << 20, "2-MiB chunks, seed 12345 again: other chunks only"},
+                                                                          {(size_t)16 << 20, "16-MiB chunks, seed 12345"}};
+            cf* xb[3] = {nullptr, nullptr, nullptr};
+            for (int i = 0; i < 3 && rc == BH_OK && room_for_one_more(); ++i) {
+                if (dev_alloc_variant(ctx->device, bytes, extra[i].chunk, 12345, (void**)&xb[i]) != hipSuccess) {
+                    (void)hipGetLastError();
+                    xb[i] = nullptr;
+                    break;
+                }
+                Probe p;
+                if ((rc = probe(xb[i], &p)) == BH_OK)
+                    fprintf(stderr, "[bh tune survey] +%d Y fwd %.3f  Z %.3f  Y inv %.3f  update X %.3f ms  (%s)\n", i, p.t[0], p.t[1], p.t[2],
+                            p.t[3], extra[i].what);
+            }
+            for (cf* b : xb)
+                if (b) (void)dev_free(b);
+        }
+    }
     for (int i = 0; i < n; ++i)
-        if (i != best && cand[i]) (void)dev_free(cand[i]);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *spec = cand[best];
+        if (i != dec.keep && cand[i]) (void)dev_free(cand[i]);
+    if (debug) {
+        char line[512];
+        int at = 0;
+        for (int i = 0; i < n && at < (int)sizeof(line) - 16; ++i) at += snprintf(line + at, sizeof(line) - at, " %.3f", ms[i]);
+        const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        fprintf(stderr, "[bh tune] Y fwd + Z + Y inv on %d spectrum allocation(s) of %.2f GB:%s ms -> #%d  (audition %.0f ms)\n", n,
+                bytes / 1e9, line, dec.keep, wall);
+    }
+    *spec = cand[dec.keep];
     return rc;
 }
 

@@ -53,7 +53,8 @@ bool fftconv_rows_wave_private(int64_t Y, int64_t X);
 int fftconv_plan(bh_ctx* ctx, int64_t Z, int64_t Y, int64_t X, ConvPlan** out);
 int fftconv_plan_tag(const ConvPlan& pl);
 size_t fftconv_spectrum_elems(const ConvPlan& pl);
-int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, float* est, size_t bytes, cf** spec);
+int fftconv_tune_spectrum(bh_ctx* ctx, const ConvPlan& pl, const cf* otf, bool otf_real, int zr, bool zreal, float* est, size_t bytes,
+                          cf** spec);
 void fftconv_arm_rowsums(ConvPlan& pl, double* dst);
 bool fftconv_rowsums_taken(ConvPlan& pl);
 
