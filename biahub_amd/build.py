@@ -39,7 +39,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "common.hpp", INCLUDE / "bhcore.h"] + [CSRC / i for v in INCLUDES.values() for i in v]
+    deps = [CSRC / s for s in SOURCES] + [CSRC / "common.hpp", CSRC / "reduce.hpp", INCLUDE / "bhcore.h"] + [CSRC / i for v in INCLUDES.values() for i in v]
     return any(d.stat().st_mtime > t for d in deps)
 
 
@@ -54,7 +54,7 @@ def build(force: bool = False, verbose: bool = True) -> Path:
     def compile_one(src: str) -> Path:
         obj = objdir / (src + ".o")
         srcp = CSRC / src
-        hdr_t = max([(CSRC / "common.hpp").stat().st_mtime, (INCLUDE / "bhcore.h").stat().st_mtime]
+        hdr_t = max([(CSRC / "common.hpp").stat().st_mtime, (CSRC / "reduce.hpp").stat().st_mtime, (INCLUDE / "bhcore.h").stat().st_mtime]
                     + [(CSRC / i).stat().st_mtime for i in INCLUDES.get(src, ())])
         if not force and obj.exists() and obj.stat().st_mtime > max(srcp.stat().st_mtime, hdr_t):
             return obj

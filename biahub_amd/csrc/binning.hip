@@ -32,32 +32,16 @@ __global__ __launch_bounds__(256) void bin_reduce_kernel(const TIN* __restrict__
         mx = fmaxf(mx, s);
     }
     __shared__ float smn[256], smx[256];
-    smn[threadIdx.x] = mn, smx[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + o]);
-            smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + o]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[2 * blockIdx.x] = smn[0], part[2 * blockIdx.x + 1] = smx[0];
+    mn = tree_reduce<256>(mn, op_min(), smn), mx = tree_reduce<256>(mx, op_max(), smx);
+    if (threadIdx.x == 0) part[2 * blockIdx.x] = mn, part[2 * blockIdx.x + 1] = mx;
 }
 
 __global__ __launch_bounds__(256) void bin_minmax_final_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
     __shared__ float smn[256], smx[256];
     float mn = INFINITY, mx = -INFINITY;
     for (int i = threadIdx.x; i < n; i += 256) mn = fminf(mn, part[2 * i]), mx = fmaxf(mx, part[2 * i + 1]);
-    smn[threadIdx.x] = mn, smx[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            smn[threadIdx.x] = fminf(smn[threadIdx.x], smn[threadIdx.x + o]);
-            smx[threadIdx.x] = fmaxf(smx[threadIdx.x], smx[threadIdx.x + o]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = smn[0], out[1] = smx[0];
+    mn = tree_reduce<256>(mn, op_min(), smn), mx = tree_reduce<256>(mx, op_max(), smx);
+    if (threadIdx.x == 0) out[0] = mn, out[1] = mx;
 }
 
 template <typename TOUT>

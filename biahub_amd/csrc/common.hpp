@@ -5,6 +5,7 @@
 #include <hipfft/hipfft.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "bhcore.h"
+#include "reduce.hpp"
 
 namespace bh {
 
@@ -206,10 +208,9 @@ struct FillStats {
     int fallback;                 // one-pass deskew: 1 = a data-dependent zero was seen, the mask pipeline re-runs the volume
 };
 
-// |value| and flat index of a running argmax (np.argmax semantics: the FIRST occurrence of the maximum wins)
-struct ArgMax {
-    float v;
-    long long i;
-};
+// |value| and flat index of a running argmax (np.argmax semantics, first_max<float> of reduce.hpp: the FIRST occurrence of the
+// maximum wins).  The FFT engine's fused peak search writes these 16 bytes.
+using ArgMax = ValIdx<float>;
+static_assert(sizeof(ArgMax) == 16 && offsetof(ArgMax, v) == 0 && offsetof(ArgMax, i) == 8, "ArgMax: a float at 0, a long long at 8");
 
 }  // namespace bh

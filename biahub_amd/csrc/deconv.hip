@@ -17,26 +17,13 @@
 
 namespace bh {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_down(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // sum of the PSF in double (wavefront reduction -> one partial per block -> host-free finalize)
 __global__ __launch_bounds__(256) void psf_sum_kernel(const float* __restrict__ psf, int64_t n, double* out) {
     __shared__ double sh[4];
     double s = 0;
     for (int64_t i = threadIdx.x; i < n; i += 256) s += (double)psf[i];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *out = sh[0] + sh[1] + sh[2] + sh[3];
+    s = block_reduce<4>(s, op_sum(), sh);
+    if (threadIdx.x == 0) *out = s;
 }
 
 // scatter the (optionally normalised, optionally origin-centred) PSF into a zeroed volume.
@@ -72,13 +59,8 @@ __global__ __launch_bounds__(256) void abs_max_kernel(const cf* __restrict__ spe
         m = fmaxf(m, a);
     }
     __shared__ float sh[4];
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-        atomicMax(gmax, __float_as_uint(m));
-    }
+    m = block_reduce<4>(m, op_max(), sh);  // a maximum of non-negative, non-NaN values: any order gives the same bits
+    if (threadIdx.x == 0) atomicMax(gmax, __float_as_uint(m));
 }
 
 // expand the half-spectrum magnitude to the reference's full (Z,Y,X) array, dividing by the max
@@ -393,10 +375,6 @@ __global__ void pcc_product_kernel(const cf* f1, const cf* f2, cf* dst, int64_t 
     }
 }
 
-__device__ __forceinline__ ArgMax better(ArgMax a, ArgMax b) {  // np.argmax: first occurrence of the maximum
-    if (b.v > a.v || (b.v == a.v && b.i < a.i)) return b;
-    return a;
-}
 // |corr| argmax (first occurrence) + optional fftshift(|corr|) output, one pass
 __global__ __launch_bounds__(256) void pcc_argmax_kernel(const float* __restrict__ corr, float* __restrict__ shifted,
                                                          int64_t Z, int64_t Y, int64_t X, ArgMax* partial) {
@@ -412,25 +390,15 @@ __global__ __launch_bounds__(256) void pcc_argmax_kernel(const float* __restrict
         }
     }
     __shared__ ArgMax sh[256];
-    sh[threadIdx.x] = best;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sh[threadIdx.x] = better(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+    best = tree_reduce<256>(best, first_max<float>(), sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = best;
 }
 __global__ __launch_bounds__(256) void pcc_argmax_final_kernel(const ArgMax* partial, int n, ArgMax* out) {
     __shared__ ArgMax sh[256];
     ArgMax best = {-1.0f, 0};
-    for (int i = threadIdx.x; i < n; i += 256) best = better(best, partial[i]);
-    sh[threadIdx.x] = best;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sh[threadIdx.x] = better(sh[threadIdx.x], sh[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0];
+    for (int i = threadIdx.x; i < n; i += 256) best = first_max<float>()(best, partial[i]);
+    best = tree_reduce<256>(best, first_max<float>(), sh);
+    if (threadIdx.x == 0) *out = best;
 }
 
 static inline dim3 grid_for(bh_ctx* ctx, int64_t n, int tb = 256) {

@@ -105,19 +105,14 @@ __device__ __forceinline__ void store_row4(float* orow, int xo, int Xp, f4u v) {
     }
 }
 
-// Sum of the workgroup's float64 partials into *dst: shuffle-reduce per wavefront, then thread 0 adds the wavefronts in order.
+// Sum of the workgroup's float64 partials into *dst, in block_reduce's order.  The wave totals' LDS is declared here and not in
+// the two kernels: declared there, four instantiations of deskew_kernel (TX 64, J 4, N 3, fill prologue) take 74 VGPRs for 72 and
+// lose a wave per SIMD (profiles/reduce_header_ab.txt).
 template <int NT>
 __device__ __forceinline__ void block_sum_store(double tsum, double* dst) {
     __shared__ double wsum[NT / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) tsum += __shfl_down(tsum, o, 64);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = tsum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < NT / 64; ++w) t += wsum[w];
-        *dst = t;
-    }
+    tsum = block_reduce<NT / 64>(tsum, op_sum(), wsum);
+    if (threadIdx.x == 0) *dst = tsum;
 }
 
 // NK > 0: N == NK known at compile time (interpolation plan kept in registers).

@@ -86,9 +86,7 @@ __global__ __launch_bounds__(256) void row_sums_kernel(const TIN* __restrict__ i
         } else {
             for (int i = lane; i < X; i += 64) s0 += (double)to_f32(rp[i]);
         }
-        double s = (s0 + s1) + (s2 + s3);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        const double s = wave_reduce((s0 + s1) + (s2 + s3), op_sum());
         if (lane == 0) R[row] = s;
     }
 }
@@ -116,20 +114,11 @@ __global__ __launch_bounds__(256) void mean_partial_kernel(DeskewGeom g, const u
     }
     __shared__ double shs[4];
     __shared__ unsigned long long shc[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_down(s, o, 64);
-        c += __shfl_down(c, o, 64);
-    }
-    if (lane == 0) {
-        shs[wave] = s;
-        shc[wave] = c;
-    }
-    __syncthreads();
+    wave_totals<4>(s, op_sum(), shs);
+    c = block_reduce<4>(c, op_sum(), shc);
     if (threadIdx.x == 0) {
-        psum[a] = (shs[0] + shs[1]) + (shs[2] + shs[3]);
-        pcnt[a] = shc[0] + shc[1] + shc[2] + shc[3];
+        psum[a] = (shs[0] + shs[1]) + (shs[2] + shs[3]);  // pairwise, not block_reduce's left to right: this order is part of the result
+        pcnt[a] = c;
     }
 }
 
@@ -146,22 +135,14 @@ __global__ __launch_bounds__(256) void mean_final_kernel(const double* __restric
             c += pcnt[i];
         }
     }
-    ss[threadIdx.x] = s;
-    sc[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            ss[threadIdx.x] += ss[threadIdx.x + o];
-            sc[threadIdx.x] += sc[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    s = tree_reduce<256>(s, op_sum(), ss);
+    c = tree_reduce<256>(c, op_sum(), sc);
     if (threadIdx.x == 0) {
-        const double nvalid = (double)sc[0] * (double)X;
-        st->sum_all = ss[0] / (double)N;
+        const double nvalid = (double)c * (double)X;
+        st->sum_all = s / (double)N;
         st->sum_shell = 0.0;
-        st->n_masked = (unsigned long long)total - (unsigned long long)(sc[0] * (unsigned long long)X);
-        st->fill = fill_mode == BH_FILL_MEAN ? (float)((ss[0] / (double)N) / nvalid) : fill_value;  // 0/0 -> NaN like torch's empty mean
+        st->n_masked = (unsigned long long)total - (unsigned long long)(c * (unsigned long long)X);
+        st->fill = fill_mode == BH_FILL_MEAN ? (float)((s / (double)N) / nvalid) : fill_value;  // 0/0 -> NaN like torch's empty mean
         st->fallback = 0;
     }
 }

@@ -17,17 +17,6 @@ namespace bh {
 #define BH_FILL_ENABLED(enable) \
     if ((enable) != nullptr && *(enable) == 0) return
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // pass 0: zero mask bits + per-block partial sum.  One wave handles 64 consecutive x of one row
 // per step; W32 = words per row (even).
 __global__ __launch_bounds__(256) void mask0_kernel(const float* __restrict__ data, uint32_t* __restrict__ m0,
@@ -51,10 +40,8 @@ __global__ __launch_bounds__(256) void mask0_kernel(const float* __restrict__ da
         }
     }
     __shared__ double sh[4];
-    s = wave_sum(s);
-    if (lane == 0) sh[wave] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    s = block_reduce<4>(s, op_sum(), sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // dilate along x inside each row of W32 words by radius r (< 32)
@@ -166,17 +153,11 @@ __global__ __launch_bounds__(256) void shell_kernel(const float* __restrict__ da
     }
     __shared__ double shs[4];
     __shared__ unsigned long long shc[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    s = wave_sum(s);
-    c = wave_sum_u64(c);
-    if (lane == 0) {
-        shs[wave] = s;
-        shc[wave] = c;
-    }
-    __syncthreads();
+    s = block_reduce<4>(s, op_sum(), shs);
+    c = block_reduce<4>(c, op_sum(), shc);
     if (threadIdx.x == 0) {
-        psum[blockIdx.x] = shs[0] + shs[1] + shs[2] + shs[3];
-        pcnt[blockIdx.x] = shc[0] + shc[1] + shc[2] + shc[3];
+        psum[blockIdx.x] = s;
+        pcnt[blockIdx.x] = c;
     }
 }
 
@@ -206,25 +187,16 @@ __global__ __launch_bounds__(FIN_NT) void finalize_kernel(const double* __restri
         s += p_shell[i];
         c += p_cnt[i];
     }
-    sa[threadIdx.x] = a;
-    ss[threadIdx.x] = s;
-    sc[threadIdx.x] = c;
-    __syncthreads();
-    for (int o = FIN_NT / 2; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            sa[threadIdx.x] += sa[threadIdx.x + o];
-            ss[threadIdx.x] += ss[threadIdx.x + o];
-            sc[threadIdx.x] += sc[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
+    a = tree_reduce<FIN_NT>(a, op_sum(), sa);
+    s = tree_reduce<FIN_NT>(s, op_sum(), ss);
+    c = tree_reduce<FIN_NT>(c, op_sum(), sc);
     if (threadIdx.x == 0) {
-        st->sum_all = sa[0];
-        st->sum_shell = ss[0];
-        st->n_masked = sc[0];
+        st->sum_all = a;
+        st->sum_shell = s;
+        st->n_masked = c;
         if (fill_mode == BH_FILL_MEAN) {
-            const double nvalid = (double)(total - sc[0]);
-            st->fill = (float)((sa[0] - ss[0]) / nvalid);  // 0/0 -> NaN like torch's empty mean
+            const double nvalid = (double)(total - c);
+            st->fill = (float)((a - s) / nvalid);  // 0/0 -> NaN like torch's empty mean
         } else {
             st->fill = fill_value;
         }

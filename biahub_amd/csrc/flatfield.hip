@@ -311,13 +311,8 @@ __global__ __launch_bounds__(256) void ff_sum_partial_kernel(const double* __res
     double a = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) a += v[i];
     __shared__ double red[256];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    a = tree_reduce<256>(a, op_sum(), red);
+    if (threadIdx.x == 0) part[blockIdx.x] = a;
 }
 
 __global__ __launch_bounds__(256) void ff_sum_final_kernel(const double* __restrict__ part, int n, double inv_count,
@@ -325,13 +320,8 @@ __global__ __launch_bounds__(256) void ff_sum_final_kernel(const double* __restr
     __shared__ double red[256];
     double a = 0;
     for (int i = threadIdx.x; i < n; i += 256) a += part[i];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0] * inv_count;
+    a = tree_reduce<256>(a, op_sum(), red);
+    if (threadIdx.x == 0) out[0] = a * inv_count;
 }
 
 // one thread per pixel, walking Z: the pattern value is read once, every access is coalesced along x

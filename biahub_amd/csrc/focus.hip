@@ -115,10 +115,8 @@ __global__ __launch_bounds__(256) void focus_stage_kernel(const TI* __restrict__
             acc += (double)v;
         }
     }
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    acc = block_reduce<4>(acc, op_sum(), red);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // n values -> out[0], one workgroup, fixed order
@@ -126,10 +124,8 @@ __global__ __launch_bounds__(256) void focus_sum_kernel(const double* __restrict
     __shared__ double red[4];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += v[i];
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = ((red[0] + red[1]) + red[2]) + red[3];
+    acc = block_reduce<4>(acc, op_sum(), red);
+    if (threadIdx.x == 0) out[0] = acc;
 }
 
 // spec: (nb, Y, nh) half spectra.  Wavefront (r, slice): rowpart[slice * nr + r] = sum over rows[r]'s interval of w |F|,
@@ -146,7 +142,7 @@ __global__ __launch_bounds__(256) void focus_band_rows_kernel(const float2* __re
         const double m = sqrt((double)f.x * (double)f.x + (double)f.y * (double)f.y);
         acc += (k == 0 || k == half) ? m : 2.0 * m;
     }
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+    acc = wave_reduce(acc, op_sum());
     if (lane == 0) rowpart[(int64_t)blockIdx.y * nr + r] = acc;
 }
 
@@ -155,10 +151,8 @@ __global__ __launch_bounds__(256) void focus_band_slices_kernel(const double* __
     const double* p = rowpart + (int64_t)blockIdx.x * nr;
     double acc = 0.0;
     for (int i = threadIdx.x; i < nr; i += 256) acc += p[i];
-    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) power[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    acc = block_reduce<4>(acc, op_sum(), red);
+    if (threadIdx.x == 0) power[blockIdx.x] = acc;
 }
 
 // The batched 2-D real float32 plan of nb (Y, X) slices: one cached set per (nb, Y, X), so a shorter last chunk has its own.

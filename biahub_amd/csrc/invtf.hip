@@ -50,13 +50,8 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restri
     }
     for (int64_t j = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += stride) a1 += (double)x[j];
     const double acc = (a0 + a1) + (a2 + a3);
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+    const double t = tree_reduce<256>(acc, op_sum(), sh);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 __global__ void sum_finish_kernel(double* part, int nblocks, int64_t n) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -425,7 +420,7 @@ __global__ void absmax_kernel(const cf* __restrict__ a, int64_t n, unsigned int*
     float m = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         m = fmaxf(m, sqrtf(a[i].x * a[i].x + a[i].y * a[i].y));
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
+    m = wave_reduce(m, op_max());
     if ((threadIdx.x & 63) == 0) atomicMax(mx, __float_as_uint(m));  // non-negative floats order like their bit patterns
 }
 __global__ void scale_by_max_kernel(const cf* __restrict__ a, cf* __restrict__ out, int64_t n, const unsigned int* __restrict__ mx) {

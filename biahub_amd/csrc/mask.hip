@@ -34,22 +34,16 @@ __global__ __launch_bounds__(256) void valid_mask_kernel(const T* __restrict__ v
         }
     }
     __shared__ unsigned long long sh[4];
-    if (lane == 0) sh[wave] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    cnt = block_reduce<4>(cnt, op_sum(), sh);  // only lane 0 of a wave counted: the other lanes add 0
+    if (threadIdx.x == 0) partial[blockIdx.x] = cnt;
 }
 
 __global__ void sum_partials_kernel(const unsigned long long* __restrict__ partial, int n, unsigned long long* __restrict__ out) {
     __shared__ unsigned long long sh[256];
     unsigned long long s = 0;
     for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sh[0];
+    s = tree_reduce<256>(s, op_sum(), sh);
+    if (threadIdx.x == 0) *out = s;
 }
 
 __global__ void bits_and_kernel(uint32_t* __restrict__ acc, const uint32_t* __restrict__ src, int64_t nwords) {

@@ -48,6 +48,25 @@ struct MomPart {  // one item, or one slice
     typename MomAcc<T>::Q q;
 };
 
+// the wave totals of a workgroup, one array per field, and the fold of the six fields: every field by block_reduce (the 64 lanes
+// in a butterfly, the four waves in order), valid on thread 0; the last call's trailing barrier lets a loop fold again
+template <typename T>
+struct MomRed {
+    unsigned long long n_nan[MOM_WAVES], n_zero[MOM_WAVES];
+    double mn[MOM_WAVES], mx[MOM_WAVES];
+    typename MomAcc<T>::S s[MOM_WAVES];
+    typename MomAcc<T>::Q q[MOM_WAVES];
+    __device__ __forceinline__ MomPart<T> fold(MomPart<T> r) {
+        r.n_nan = block_reduce<MOM_WAVES>(r.n_nan, op_sum(), n_nan);
+        r.n_zero = block_reduce<MOM_WAVES>(r.n_zero, op_sum(), n_zero);
+        r.mn = block_reduce<MOM_WAVES>(r.mn, op_min(), mn);
+        r.mx = block_reduce<MOM_WAVES>(r.mx, op_max(), mx);
+        r.s = block_reduce<MOM_WAVES>(r.s, op_sum(), s);
+        r.q = block_reduce<MOM_WAVES, true>(r.q, op_sum(), q);
+        return r;
+    }
+};
+
 // lane-private running state of one item
 template <typename T>
 struct MomLane {
@@ -108,7 +127,7 @@ __global__ __launch_bounds__(MOM_NT) void moments_items_kernel(const T* __restri
                                                                int rows, int nblk, int64_t nitems, double centre, MomPart<T>* __restrict__ part) {
     constexpr int V = 16 / (int)sizeof(T);
     typedef T VT __attribute__((ext_vector_type(V)));
-    __shared__ MomPart<T> red[MOM_WAVES];
+    __shared__ MomRed<T> red;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
         const int64_t z = item / nblk;
@@ -139,33 +158,15 @@ __global__ __launch_bounds__(MOM_NT) void moments_items_kernel(const T* __restri
         if constexpr (MomAcc<T>::is_float) r.mn = (double)a.fmn, r.mx = (double)a.fmx;
         else r.mn = a.imn == INT_MAX ? (double)INFINITY : (double)a.imn, r.mx = a.imx == INT_MIN ? -(double)INFINITY : (double)a.imx;
         r.s = a.s, r.q = a.q;
-        for (int d = 32; d > 0; d >>= 1) {
-            r.n_nan += __shfl_xor(r.n_nan, d);
-            r.n_zero += __shfl_xor(r.n_zero, d);
-            r.mn = fmin(r.mn, __shfl_xor(r.mn, d));
-            r.mx = fmax(r.mx, __shfl_xor(r.mx, d));
-            r.s += __shfl_xor(r.s, d);
-            r.q += __shfl_xor(r.q, d);
-        }
-        if (lane == 0) red[wave] = r;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            MomPart<T> o = red[0];
-            for (int w = 1; w < MOM_WAVES; ++w) {
-                o.n_nan += red[w].n_nan, o.n_zero += red[w].n_zero;
-                o.mn = fmin(o.mn, red[w].mn), o.mx = fmax(o.mx, red[w].mx);
-                o.s += red[w].s, o.q += red[w].q;
-            }
-            part[item] = o;
-        }
-        __syncthreads();  // red is written again by the next item
+        r = red.fold(r);  // its trailing barrier: red is written again by the next item
+        if (threadIdx.x == 0) part[item] = r;
     }
 }
 
 // slice blockIdx.x: thread t takes items t, t + 256, ..., then the same butterfly and wave order as above
 template <typename T>
 __global__ __launch_bounds__(MOM_NT) void moments_slices_kernel(const MomPart<T>* __restrict__ part, int nblk, bh_moments* __restrict__ out) {
-    __shared__ MomPart<T> red[MOM_WAVES];
+    __shared__ MomRed<T> red;
     const MomPart<T>* p = part + (int64_t)blockIdx.x * nblk;
     MomPart<T> r;
     r.n_nan = 0, r.n_zero = 0, r.mn = INFINITY, r.mx = -INFINITY, r.s = 0, r.q = 0;
@@ -175,23 +176,8 @@ __global__ __launch_bounds__(MOM_NT) void moments_slices_kernel(const MomPart<T>
         r.mn = fmin(r.mn, v.mn), r.mx = fmax(r.mx, v.mx);
         r.s += v.s, r.q += v.q;
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        r.n_nan += __shfl_xor(r.n_nan, d);
-        r.n_zero += __shfl_xor(r.n_zero, d);
-        r.mn = fmin(r.mn, __shfl_xor(r.mn, d));
-        r.mx = fmax(r.mx, __shfl_xor(r.mx, d));
-        r.s += __shfl_xor(r.s, d);
-        r.q += __shfl_xor(r.q, d);
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
-    __syncthreads();
+    const MomPart<T> o = red.fold(r);
     if (threadIdx.x == 0) {
-        MomPart<T> o = red[0];
-        for (int w = 1; w < MOM_WAVES; ++w) {
-            o.n_nan += red[w].n_nan, o.n_zero += red[w].n_zero;
-            o.mn = fmin(o.mn, red[w].mn), o.mx = fmax(o.mx, red[w].mx);
-            o.s += red[w].s, o.q += red[w].q;
-        }
         bh_moments m;
         m.n_nan = o.n_nan, m.n_zero = o.n_zero, m.min = o.mn, m.max = o.mx;
         if constexpr (MomAcc<T>::is_float) m.isum = 0, m.isumsq = 0, m.fsum = o.s, m.fsumsq = o.q;

@@ -58,22 +58,11 @@ __global__ __launch_bounds__(256) void block_peaks_kernel(const float* __restric
         const long long idx = ((long long)z * p.Y + y) * p.X + x;
         if (v > best || (v == best && idx < bidx)) best = v, bidx = idx;
     }
-    __shared__ float sv[256];
-    __shared__ long long si[256];
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bidx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const float v = sv[threadIdx.x + o];
-            const long long j = si[threadIdx.x + o];
-            if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && j < si[threadIdx.x])) sv[threadIdx.x] = v, si[threadIdx.x] = j;
-        }
-        __syncthreads();
-    }
+    __shared__ ArgMax sh[256];
+    const ArgMax top = tree_reduce<256>(ArgMax{best, bidx}, first_max<float>(), sh);
     if (threadIdx.x == 0) {
-        values[b] = sv[0];
-        indices[b] = si[0] == 0x7fffffffffffffffll ? 0 : si[0];
+        values[b] = top.v;
+        indices[b] = top.i == 0x7fffffffffffffffll ? 0 : top.i;
     }
 }
 
@@ -119,20 +108,9 @@ __global__ __launch_bounds__(256) void patch_argmax_kernel(const float* __restri
         const float v = s[i];
         if (v > best) best = v, bidx = i;
     }
-    __shared__ float sv[256];
-    __shared__ long long si[256];
-    sv[threadIdx.x] = best;
-    si[threadIdx.x] = bidx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const float v = sv[threadIdx.x + o];
-            const long long j = si[threadIdx.x + o];
-            if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && j < si[threadIdx.x])) sv[threadIdx.x] = v, si[threadIdx.x] = j;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) peaks[blockIdx.x] = si[0] == 0x7fffffffffffffffll ? 0 : si[0];
+    __shared__ ArgMax sh[256];
+    const ArgMax top = tree_reduce<256>(ArgMax{best, bidx}, first_max<float>(), sh);
+    if (threadIdx.x == 0) peaks[blockIdx.x] = top.i == 0x7fffffffffffffffll ? 0 : top.i;
 }
 
 __global__ __launch_bounds__(256) void patch_max_kernel(const float* __restrict__ vol, const int* __restrict__ starts,
@@ -145,13 +123,8 @@ __global__ __launch_bounds__(256) void patch_max_kernel(const float* __restrict_
         m = fmaxf(m, vol[((size_t)(starts[3 * b] + z) * p.Y + (starts[3 * b + 1] + y)) * p.X + starts[3 * b + 2] + x]);
     }
     __shared__ float sv[256];
-    sv[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sv[threadIdx.x] = fmaxf(sv[threadIdx.x], sv[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) maxes[b] = sv[0];
+    m = tree_reduce<256>(m, op_max(), sv);
+    if (threadIdx.x == 0) maxes[b] = m;
 }
 
 // out[v] = mean_b patch_b[v] / max_b : one thread per patch voxel, beads in order (float64 accumulate)
@@ -173,16 +146,7 @@ __global__ __launch_bounds__(1024) void psf_normalise_kernel(float* __restrict__
     __shared__ float smin[1024], smax[1024];
     float mn = INFINITY, mx = -INFINITY;
     for (long long i = threadIdx.x; i < n; i += 1024) mn = fminf(mn, a[i]), mx = fmaxf(mx, a[i]);
-    smin[threadIdx.x] = mn, smax[threadIdx.x] = mx;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            smin[threadIdx.x] = fminf(smin[threadIdx.x], smin[threadIdx.x + o]);
-            smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + o]);
-        }
-        __syncthreads();
-    }
-    const float lo = smin[0], hi = smax[0] - smin[0];
+    const float lo = tree_reduce<1024>(mn, op_min(), smin), hi = tree_reduce<1024>(mx, op_max(), smax) - lo;
     for (long long i = threadIdx.x; i < n; i += 1024) a[i] = (a[i] - lo) / hi;
 }
 

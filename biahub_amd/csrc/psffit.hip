@@ -129,26 +129,6 @@ __global__ __launch_bounds__(FIT_THREADS) void psf_bg_kernel(FitArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------------- block reductions
-// sum of a[k] over the block, k < N, into out[k] (LDS): lanes by shuffle, then the waves in wave order.  red: FIT_WAVES * N.
-template <typename T, int N>
-__device__ void block_sum(T (&a)[N], T* red, T* out) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[k] += __shfl_down(a[k], o);
-        if (lane == 0) red[wave * N + k] = a[k];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) {
-        T s = red[threadIdx.x];
-        for (int w = 1; w < FIT_WAVES; ++w) s += red[w * N + threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-    __syncthreads();
-}
-
 // ------------------------------------------------------------------------------------------------------------ the models
 template <int D>
 struct Dim {
@@ -254,7 +234,7 @@ __device__ void accumulate(const FitArgs& a, const Patch& pt, int M, const doubl
         for (int i = 0; i < P; ++i) acc[NA + i] += J[i] * r;
         acc[NA + P] += r * r;
     }
-    block_sum<double, NACC>(acc, red, out);
+    block_reduce_n<FIT_WAVES, NACC>(acc, op_sum(), red, out);
 }
 
 // ------------------------------------------------------------------------------------- the small dense algebra (thread 0)
@@ -390,20 +370,17 @@ __global__ __launch_bounds__(FIT_THREADS) void psf_fit_kernel(FitArgs a) {
 #pragma unroll
         for (int i = 0; i < D; ++i) m_[1 + i] += v * idx[i], m_[1 + D + i] += v * idx[i] * idx[i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) vmax = max(vmax, __shfl_down(vmax, o));
-    if ((threadIdx.x & 63) == 0) vmax_w[threadIdx.x >> 6] = vmax;
-    block_sum<long long, NMOM>(m_, mred, mom);
+    vmax = block_reduce<FIT_WAVES>(vmax, op_max(), vmax_w);
+    block_reduce_n<FIT_WAVES, NMOM>(m_, op_sum(), mred, mom);
     if (threadIdx.x == 0) {
         int status = -1;
-        for (int w = 1; w < FIT_WAVES; ++w) vmax_w[0] = max(vmax_w[0], vmax_w[w]);
         if (bg < 0 || mom[0] == 0) {
             status = bg < 0 ? BH_PSF_NONFINITE : BH_PSF_EMPTY;
             for (int i = 0; i < P; ++i) par[i] = NAN;
         } else {
             const double sw = (double)mom[0];
             par[0] = (double)bg;
-            par[1] = (double)((long long)vmax_w[0] - bg);
+            par[1] = (double)((long long)vmax - bg);
             for (int i = 0; i < D; ++i) {
                 const double s = a.sp[Dim<D>::AX0 + i], swi = (double)mom[1 + i], swii = (double)mom[1 + D + i];
                 par[2 + i] = swi / sw * s;

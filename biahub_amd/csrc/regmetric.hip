@@ -33,7 +33,8 @@ constexpr int ST_NT = 256;
 __global__ __launch_bounds__(ST_NT) void stats_partial_kernel(const float* __restrict__ in, int Z, int Y, int X,
                                                               double* __restrict__ part) {
     // one row (z, y) per wave iteration: lanes along x; row sums are weighted by z and y once per row
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = ST_NT / 64;
+    constexpr int nw = ST_NT / 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long rows = (long long)Z * Y;
     float mn = INFINITY, mx = -INFINITY;
     double s = 0, sz = 0, sy = 0, sx = 0;
@@ -53,28 +54,13 @@ __global__ __launch_bounds__(ST_NT) void stats_partial_kernel(const float* __res
         sz += rs * (double)z;
         sy += rs * (double)y;
     }
-    __shared__ double red[ST_NT / 64][6];
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, o));
-        mx = fmaxf(mx, __shfl_down(mx, o));
-        s += __shfl_down(s, o);
-        sz += __shfl_down(sz, o);
-        sy += __shfl_down(sy, o);
-        sx += __shfl_down(sx, o);
-    }
-    if (lane == 0) {
-        red[wave][0] = mn, red[wave][1] = mx, red[wave][2] = s, red[wave][3] = sz, red[wave][4] = sy, red[wave][5] = sx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double o[6] = {red[0][0], red[0][1], red[0][2], red[0][3], red[0][4], red[0][5]};
-        for (int w = 1; w < nw; ++w) {
-            o[0] = fmin(o[0], red[w][0]);
-            o[1] = fmax(o[1], red[w][1]);
-            for (int k = 2; k < 6; ++k) o[k] += red[w][k];
-        }
+    __shared__ float redf[2][nw];
+    __shared__ double red[4][nw];
+    const double o[6] = {(double)block_reduce<nw>(mn, op_min(), redf[0]), (double)block_reduce<nw>(mx, op_max(), redf[1]),
+                         block_reduce<nw>(s, op_sum(), red[0]),           block_reduce<nw>(sz, op_sum(), red[1]),
+                         block_reduce<nw>(sy, op_sum(), red[2]),          block_reduce<nw>(sx, op_sum(), red[3])};
+    if (threadIdx.x == 0)
         for (int k = 0; k < 6; ++k) part[(size_t)blockIdx.x * 6 + k] = o[k];
-    }
 }
 
 // fixed-order tree over the per-workgroup partials: column k of `part` (n rows, `cols` columns) -> out[k]
@@ -89,17 +75,9 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const double* __re
             const double v = part[(size_t)i * cols + k];
             a = op == 1 ? fmin(a, v) : (op == 2 ? fmax(a, v) : a + v);
         }
-        red[threadIdx.x] = a;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) {
-                const double b = red[threadIdx.x + o];
-                red[threadIdx.x] = op == 1 ? fmin(red[threadIdx.x], b) : (op == 2 ? fmax(red[threadIdx.x], b) : red[threadIdx.x] + b);
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[k] = red[0];
-        __syncthreads();
+        // red is written again by the next column: the trailing barrier
+        a = op == 1 ? tree_reduce<256, true>(a, op_min(), red) : (op == 2 ? tree_reduce<256, true>(a, op_max(), red) : tree_reduce<256, true>(a, op_sum(), red));
+        if (threadIdx.x == 0) out[k] = a;
     }
 }
 
@@ -259,7 +237,7 @@ __global__ __launch_bounds__(MI_NT) void mi_hist_kernel(const float* __restrict_
                 }
             }
         }
-        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        cnt = wave_reduce(cnt, op_sum());
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(nvalid, (unsigned long long)cnt);
         __syncthreads();
         for (int i = threadIdx.x; i < nb2; i += MI_NT)
@@ -275,14 +253,7 @@ __global__ __launch_bounds__(1024) void mi_table_kernel(const unsigned long long
     const int nb2 = bins * bins;
     double t = 0;
     for (int i = threadIdx.x; i < nb2; i += 1024) t += (double)hist[i];
-    red[threadIdx.x] = t;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const double total = red[0];
-    __syncthreads();
+    const double total = tree_reduce<1024, true>(t, op_sum(), red);  // red is written again below
     if ((int)threadIdx.x < bins) {
         double a = 0, b = 0;
         for (int k = 0; k < bins; ++k) {
@@ -304,14 +275,9 @@ __global__ __launch_bounds__(1024) void mi_table_kernel(const unsigned long long
         }
         table[i] = l;
     }
-    red[threadIdx.x] = mi;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    mi = tree_reduce<1024>(mi, op_sum(), red);
     if (threadIdx.x == 0) {
-        out[0] = red[0];
+        out[0] = mi;
         out[1] = total / (double)MI_FIX;
     }
 }
@@ -352,18 +318,8 @@ __global__ __launch_bounds__(MI_NT) void mi_grad_kernel(const float* __restrict_
             }
         }
     }
-    __shared__ double red[MI_NT / 64][12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k)
-        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o);
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 12; ++k) red[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        double a = 0;
-        for (int w = 0; w < MI_NT / 64; ++w) a += red[w][threadIdx.x];
-        part[(size_t)blockIdx.x * 12 + threadIdx.x] = a;
-    }
+    __shared__ double red[MI_NT / 64 * 12];
+    block_reduce_n<MI_NT / 64, 12>(acc, op_sum(), red, part + (size_t)blockIdx.x * 12);
 }
 
 // ------------------------------------------------------------------------------------------------ Sobel magnitude

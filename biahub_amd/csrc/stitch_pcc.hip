@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void strip_min_kernel(const StripGeom g, const
         const float v = (float)t[(int64_t)(oy + y) * g.X + ox + x];
         m = v < m ? v : m;  // a NaN is never the minimum
     }
-    for (int d = 32; d > 0; d >>= 1) m = fminf(m, __shfl_xor(m, d));
+    m = wave_reduce(m, op_min());
     if ((threadIdx.x & 63) == 0) atomicMin(&keys[s], f2key(m));
 }
 
@@ -253,10 +253,7 @@ __global__ __launch_bounds__(256) void wrap_gauss_kernel(const PeakGeom p, const
     }
 }
 
-struct PeakMax {  // a running argmax: the FIRST occurrence of the maximum wins
-    double v;
-    long long i;
-};
+using PeakMax = ValIdx<double>;  // a running argmax under first_max<double>: the FIRST occurrence of the maximum wins
 
 constexpr int SP_PB = 32;  // workgroups per edge in the two peak kernels
 
@@ -265,8 +262,6 @@ struct PeakOut {
     unsigned long long background_bits;  // a non-negative double: such doubles order like their bit patterns (atomicMax)
     long long index;                     // flat index of the peak in the crop
 };
-
-__device__ __forceinline__ bool peak_before(const PeakMax& a, const PeakMax& b) { return a.v > b.v || (a.v == b.v && a.i < b.i); }
 
 // Workgroup (k, e) takes slice k of edge e's smoothed crop: its first maximum in C order, to part[e][k].
 __global__ __launch_bounds__(256) void peak_argmax_kernel(const PeakGeom p, const double* __restrict__ sm, PeakMax* __restrict__ part) {
@@ -279,17 +274,8 @@ __global__ __launch_bounds__(256) void peak_argmax_kernel(const PeakGeom p, cons
         const double v = s[i];
         if (v > m.v) m.v = v, m.i = i;  // ascending i per thread: the first occurrence stays
     }
-    for (int d = 32; d > 0; d >>= 1) {
-        const PeakMax o{__shfl_xor(m.v, d), __shfl_xor(m.i, d)};
-        if (peak_before(o, m)) m = o;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int i = 1; i < 4; ++i)
-            if (peak_before(red[i], m)) m = red[i];
-        part[blockIdx.y * SP_PB + blockIdx.x] = m;
-    }
+    m = block_reduce<4>(m, first_max<double>(), red);
+    if (threadIdx.x == 0) part[blockIdx.y * SP_PB + blockIdx.x] = m;
 }
 
 // The edge's peak from the slices' maxima, then the largest value of this workgroup's slice outside [p - m, p + m) per axis, the
@@ -304,10 +290,7 @@ __global__ __launch_bounds__(256) void peak_background_kernel(const PeakGeom p, 
     const int64_t lo = blockIdx.x * chunk, hi = min(lo + chunk, n);
     const double* s = sm + (int64_t)blockIdx.y * n;
     PeakMax best = part[blockIdx.y * SP_PB];
-    for (int k = 1; k < SP_PB; ++k) {
-        const PeakMax o = part[blockIdx.y * SP_PB + k];
-        if (peak_before(o, best)) best = o;
-    }
+    for (int k = 1; k < SP_PB; ++k) best = first_max<double>()(best, part[blockIdx.y * SP_PB + k]);
     if (best.i >= n) best.i = 0;  // nothing compared greater than -inf (all NaN): np.argmax would name a NaN; index 0 stands in
     const int py = (int)(best.i / w), px = (int)(best.i % w);
     auto lo_of = [](int q, int m_, int len) { return q - m_ < 0 ? max(q - m_ + len, 0) : min(q - m_, len); };
@@ -319,11 +302,8 @@ __global__ __launch_bounds__(256) void peak_background_kernel(const PeakGeom p, 
         if (window && y >= ylo && y < yhi && x >= xlo && x < xhi) continue;
         bg = fmax(bg, s[i]);
     }
-    for (int d = 32; d > 0; d >>= 1) bg = fmax(bg, __shfl_xor(bg, d));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = bg;
-    __syncthreads();
+    bg = block_reduce<4>(bg, op_max(), red);
     if (threadIdx.x == 0) {
-        for (int i = 1; i < 4; ++i) bg = fmax(bg, red[i]);
         if (bg > 0.0) atomicMax(&out[blockIdx.y].background_bits, (unsigned long long)__double_as_longlong(bg));
         if (blockIdx.x == 0) out[blockIdx.y].peak = best.v, out[blockIdx.y].index = best.i;
     }
