@@ -25,6 +25,7 @@ DS_STRIDE, DS_MEAN, DS_MIN, DS_MAX, DS_MEDIAN, DS_MODE = range(6)
 PSF_NCOL, PSF_NGUESS = 55, 22  # BH_PSF_NCOL, BH_PSF_NGUESS
 GRAPH_KMAX = 16  # BH_GRAPH_KMAX
 PSF_CONVERGED, PSF_ITERCAP, PSF_NONFINITE, PSF_SINGULAR, PSF_EMPTY = range(5)
+STACKREG_CONVERGED, STACKREG_ITERCAP, STACKREG_DEGENERATE = range(3)  # BH_STACKREG_*
 (T_DESKEW, T_FILL, T_RL_TOTAL, T_TIKHONOV, T_AFFINE, T_CROPFLIP, T_RL_ITER, T_TF, T_FLATFIELD, T_MOMENTS, T_EDGECOST) = range(11)
 
 _i64, _f64, _f32, _int, _vp = C.c_int64, C.c_double, C.c_float, C.c_int, C.c_void_p
@@ -126,6 +127,8 @@ SIGNATURES = {
     "bh_average_patches": (_int, [_vp, _vp, _i64, _i64, _i64, C.POINTER(_int), _int, C.POINTER(_int), _int, _vp]),
     "bh_psf_fit": (_int, [_vp, _vp, _i64, _i64, _i64, C.POINTER(_int), C.POINTER(_int), _int, C.POINTER(_f64), _f64, _f64, _int, _int,
                           C.POINTER(_f64), C.POINTER(_f64), C.POINTER(_int), C.POINTER(_int)]),
+    "bh_stackreg_translation": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, C.POINTER(C.c_int32), _int, C.POINTER(_f64),
+                                       C.POINTER(_f64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "bh_affine": (_int, [_vp, _vp, _int, _i64, _i64, _i64, C.POINTER(_f64), _int, _int, _f32, _vp, _i64, _i64,
                          _i64, C.POINTER(_i64)]),
     "bh_spline_prefilter": (_int, [_vp, _vp, _int, _i64, _i64, _i64, _vp]),

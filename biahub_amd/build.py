@@ -14,7 +14,7 @@ INCLUDE = PKG.parent / "include"
 LIB = PKG / "libbhcore.so"
 # longest compiles first (the pool below starts sources in this order): pyramid.hip alone takes longer than any other file, then
 # the kernel families of the FFT engine
-SOURCES = ["pyramid.hip", "fftconv_col.hip", "fftconv_xtile.hip", "fftconv_xw.hip", "fftconv_colreg.hip", "deskew.hip", "stitch.hip", "stitch_pcc.hip", "focus.hip", "affine.hip", "fftconv.hip", "context.hip", "fill.hip", "deconv.hip", "spline.hip", "copy.hip", "regmetric.hip", "moments.hip", "graphmatch.hip", "flatfield.hip", "psffit.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "zstd.hip", "zstd_enc.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
+SOURCES = ["pyramid.hip", "fftconv_col.hip", "fftconv_xtile.hip", "fftconv_xw.hip", "fftconv_colreg.hip", "deskew.hip", "stitch.hip", "stitch_pcc.hip", "focus.hip", "affine.hip", "fftconv.hip", "context.hip", "fill.hip", "deconv.hip", "spline.hip", "copy.hip", "regmetric.hip", "moments.hip", "graphmatch.hip", "flatfield.hip", "psffit.hip", "stackreg.hip", "psf.hip", "binning.hip", "codec.hip", "lz4.hip", "zstd.hip", "zstd_enc.hip", "mask.hip", "invtf.hip", "host_deskew.hip"]
 ARCH = "gfx950"
 
 

@@ -20,7 +20,7 @@ from .io import create_empty_plate, open_ome_zarr, process_single_position
 from .settings import (DeconvolveSettings, DeskewSettings, EstimateRegistrationSettings,
                        EstimateStabilizationSettings, FlatFieldCorrectionSettings, FocusFindingSettings, PhaseCrossCorrSettings,
                        ProcessingImportFuncSettings, PsfFromBeadsSettings, RegistrationSettings, RichardsonLucySettings,
-                       StabilizationSettings, StitchSettings)
+                       StabilizationSettings, StackRegSettings, StitchSettings)
 from .utils.cluster import echo_resources, estimate_resources, get_submitit_cluster
 from .utils.config import model_to_yaml, settings_fingerprint, yaml_to_model
 from .utils.paths import get_output_paths, sbatch_to_submitit
@@ -703,25 +703,25 @@ def optimize_registration_cli(source_position_dirpaths, target_position_dirpaths
 @click.option("--local", "-l", is_flag=True, default=False)
 def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_filepath, sbatch_filepath, local):
     """Estimate per-timepoint stabilization transforms (reference: ``biahub estimate-stabilization``,
-    estimate_stabilization.py:1223-1640).  Three combinations run here: ``stabilization_type: xyz`` with ``stabilization_method:
-    phase-cross-corr`` (GPU phase cross-correlation; ``xyz_stabilization_settings/<fov>.yml``), ``xyz`` with ``beads`` (bead
-    matching of the first position's estimation channel against its first or neighbouring timepoint, registration/beads.py;
-    ``xyz_stabilization_settings.yml``) and ``stabilization_type: z`` with the reference's default ``focus-finding`` (GPU mid-band
-    power; ``z_stabilization_settings/<fov>.yml``, or ``average.yml`` with ``average_across_wells``).  Each file feeds
-    ``stabilize``."""
-    from .estimate_stabilization import estimate_xyz_stabilization_pcc, estimate_z_stabilization, save_transforms
+    estimate_stabilization.py:1223-1640).  The reference's five combinations run here: ``stabilization_type: xyz`` with
+    ``stabilization_method: phase-cross-corr`` (GPU phase cross-correlation; ``xyz_stabilization_settings/<fov>.yml``), ``xyz`` with
+    ``beads`` (bead matching of the first position's estimation channel against its first or neighbouring timepoint,
+    registration/beads.py; ``xyz_stabilization_settings.yml``), and with the reference's default ``focus-finding``:
+    ``stabilization_type: z`` (GPU mid-band power; ``z_stabilization_settings/<fov>.yml``, or ``average.yml`` with
+    ``average_across_wells``), ``xy`` (StackReg translation of the in-focus planes on the GPU;
+    ``xy_stabilization_settings/<fov>.yml``) and ``xyz`` (both; ``xyz_``, ``z_`` and ``xy_stabilization_settings/<fov>.yml``, xyz =
+    xy @ z per timepoint).  Each file feeds ``stabilize``."""
+    from .estimate_stabilization import (estimate_xy_stabilization, estimate_xyz_stabilization_pcc, estimate_z_stabilization,
+                                         save_transforms)
 
     settings = yaml_to_model(config_filepath, EstimateStabilizationSettings)
     click.echo(f"Settings: {settings}")
     combo = (settings.stabilization_type, settings.stabilization_method)
-    if settings.stabilization_method == "focus-finding" and settings.stabilization_type in ("xy", "xyz"):
-        raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method 'focus-finding' registers xy with "
-                               "StackReg (pystackreg), which is not available in biahub_amd; 'focus-finding' runs here with "
-                               "stabilization_type 'z', and 'xyz' with 'phase-cross-corr'.")
-    if combo not in (("xyz", "phase-cross-corr"), ("xyz", "beads"), ("z", "focus-finding")):
+    if combo not in (("xyz", "phase-cross-corr"), ("xyz", "beads"), ("z", "focus-finding"), ("xy", "focus-finding"),
+                     ("xyz", "focus-finding")):
         raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method "
                                f"{settings.stabilization_method!r} is not available in biahub_amd (only 'xyz' with "
-                               "'phase-cross-corr' or 'beads' and 'z' with 'focus-finding').")
+                               "'phase-cross-corr' or 'beads' and 'z', 'xy' or 'xyz' with 'focus-finding').")
     if settings.eval_transform_settings:
         raise click.UsageError("eval_transform_settings (transform validation / interpolation) is not available in biahub_amd")
     output_dirpath = Path(output_dirpath)
@@ -730,14 +730,33 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
         channel_index = ds.channel_names.index(settings.stabilization_estimation_channel)
         voxel_size = list(ds.scale)
         fov_yx = tuple(int(n) for n in ds.data.shape[-2:])
-    if combo == ("z", "focus-finding"):
+    if combo in (("z", "focus-finding"), ("xyz", "focus-finding")):
         from .estimate_stabilization import centre_window
 
         focus_settings = FocusFindingSettings(**(settings.focus_finding_settings or {}))
         try:
             centre_window(*fov_yx, focus_settings.center_crop_xy)
         except ValueError as e:
+            if combo[0] == "xyz":
+                raise click.UsageError(f"stabilization_type 'xyz' with method 'focus-finding' finds the z part as for 'z' and registers "
+                                       f"xy with StackReg: {e}") from None
             raise click.UsageError(str(e)) from None
+    if combo in (("xy", "focus-finding"), ("xyz", "focus-finding")):
+        from .estimate_stabilization import centre_window
+
+        stack_reg_settings = StackRegSettings(**(settings.stack_reg_settings or {}))
+        if combo[0] == "xyz" and focus_settings.average_across_wells:
+            raise click.UsageError("stabilization_type 'xyz' with method 'focus-finding' and focus_finding_settings.average_across_wells "
+                                   "is not available: the reference looks every FOV up in the z transforms, which are then keyed "
+                                   "'average', and fails")
+        nested = stack_reg_settings.focus_finding_settings or FocusFindingSettings()
+        try:
+            centre_window(*fov_yx, stack_reg_settings.center_crop_xy)
+            centre_window(*fov_yx, nested.center_crop_xy)
+        except ValueError as e:
+            raise click.UsageError(f"stabilization_type {combo[0]!r} with method 'focus-finding' registers xy with StackReg on the centre "
+                                   "window stack_reg_settings.center_crop_xy, at the focus slice, which is found as for 'z' on "
+                                   f"stack_reg_settings.focus_finding_settings.center_crop_xy: {e}") from None
     if combo == ("xyz", "beads"):
         from .registration.beads import estimate_tczyx
 
@@ -769,20 +788,43 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
         pcc = settings.phase_cross_corr_settings or PhaseCrossCorrSettings()
         fov_transforms = estimate_xyz_stabilization_pcc(input_position_dirpaths, output_dirpath, pcc, channel_index=channel_index,
                                                         sbatch_filepath=sbatch_filepath, cluster="local", verbose=settings.verbose)
-    else:
+    elif combo == ("z", "focus-finding"):
         click.echo("Estimating z stabilization parameters with focus finding")
         fov_transforms = estimate_z_stabilization(input_position_dirpaths, output_dirpath, focus_settings,
                                                   channel_index=channel_index, sbatch_filepath=sbatch_filepath, cluster="local",
                                                   verbose=settings.verbose)
+    elif combo == ("xy", "focus-finding"):
+        click.echo("Estimating xy stabilization parameters with focus finding and stack registration")
+        fov_transforms = estimate_xy_stabilization(input_position_dirpaths, output_dirpath, stack_reg_settings,
+                                                   channel_index=channel_index, sbatch_filepath=sbatch_filepath, cluster="local",
+                                                   verbose=settings.verbose)
+    else:
+        click.echo("Estimating xyz stabilization parameters with focus finding and stack registration")
+        z_transforms = estimate_z_stabilization(input_position_dirpaths, output_dirpath, focus_settings, channel_index=channel_index,
+                                                sbatch_filepath=sbatch_filepath, cluster="local", verbose=settings.verbose)
+        xy_transforms = estimate_xy_stabilization(input_position_dirpaths, output_dirpath, stack_reg_settings,
+                                                  channel_index=channel_index, sbatch_filepath=sbatch_filepath, cluster="local",
+                                                  verbose=settings.verbose)
+        fov_transforms = {}
+        for fov, xy in xy_transforms.items():  # estimate_stabilization.py:1318-1388
+            z, xy = np.asarray(z_transforms[fov]), np.asarray(xy)
+            if xy.shape[0] != z.shape[0]:
+                raise ValueError("The number of translation matrices and z drift matrices must be the same")
+            fov_transforms[fov] = np.asarray([a @ b for a, b in zip(xy, z)]).tolist()
+    written = {settings.stabilization_type: fov_transforms}
+    if combo == ("xyz", "focus-finding"):  # the parts next to the product, for the FOVs that have one
+        written["z"] = {fov: z_transforms[fov] for fov in fov_transforms}
+        written["xy"] = {fov: xy_transforms[fov] for fov in fov_transforms}
     if parallel.world_info()[0] == 0:
-        for fov, transforms in fov_transforms.items():
-            model = StabilizationSettings(stabilization_type=settings.stabilization_type,
-                                          stabilization_method=settings.stabilization_method,
-                                          stabilization_estimation_channel=settings.stabilization_estimation_channel,
-                                          stabilization_channels=settings.stabilization_channels,
-                                          affine_transform_zyx_list=[np.eye(4).tolist()], time_indices="all",
-                                          output_voxel_size=voxel_size)
-            save_transforms(model, transforms, output_dirpath / f"{settings.stabilization_type}_stabilization_settings" / f"{fov}.yml")
+        for kind, per_fov in written.items():
+            for fov, transforms in per_fov.items():
+                model = StabilizationSettings(stabilization_type=settings.stabilization_type,
+                                              stabilization_method=settings.stabilization_method,
+                                              stabilization_estimation_channel=settings.stabilization_estimation_channel,
+                                              stabilization_channels=settings.stabilization_channels,
+                                              affine_transform_zyx_list=[np.eye(4).tolist()], time_indices="all",
+                                              output_voxel_size=voxel_size)
+                save_transforms(model, transforms, output_dirpath / f"{kind}_stabilization_settings" / f"{fov}.yml")
     click.echo(f"Stabilization settings saved to {output_dirpath.resolve()}")
 
 

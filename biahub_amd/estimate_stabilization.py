@@ -1,6 +1,6 @@
 """The stabilisation estimate on MI355X — mirror of ``biahub/estimate_stabilization.py``.
 
-Two of the reference's methods run here, each around one device primitive:
+Three of the reference's estimators run here, each around one device primitive:
 
 * ``phase-cross-corr`` (``stabilization_type: xyz``; :129-310, :444-693): ``bh_phase_cross_corr`` — two R2C transforms, the
   fused normalised conjugate product, C2R, |.| + first-occurrence argmax on device — under the
@@ -8,9 +8,12 @@ Two of the reference's methods run here, each around one device primitive:
 * ``focus-finding`` (``stabilization_type: z``, the reference's default method; :900-1220): ``bh_focus_band_power`` — the
   mid-band power of every z-slice of the centre window (``biahub_amd/focus.py``) — under
   ``estimate_z_focus_per_position``, ``get_mean_z_positions`` and ``estimate_z_stabilization``.
+* StackReg translation (``stabilization_type: xy`` and ``xyz`` with ``focus-finding``; :696-897): ``bh_stackreg_translation`` —
+  the in-focus plane of every timepoint registered against the first or the previous one in one batched solve
+  (``biahub_amd/stackreg.py``) — under ``estimate_xy_stabilization[_per_position]``.
 
-Either way ``estimate-stabilization`` writes the per-timepoint 4x4 matrices ``stabilize`` consumes.  StackReg (xy) and bead
-matching are not part of this package.
+Either way ``estimate-stabilization`` writes the per-timepoint 4x4 matrices ``stabilize`` consumes.  Bead matching lives in
+``registration/beads.py``.
 """
 
 from __future__ import annotations
@@ -476,6 +479,113 @@ def estimate_z_stabilization(input_position_dirpaths, output_folder_path, focus_
         shutil.rmtree(focus_out)
         shutil.rmtree(transforms_out)
     return result
+
+
+# ----------------------------------------------------------------------------- StackReg: the xy chain (:696-897)
+def fill_focus_indices(focus_idx) -> list[int]:
+    """``estimate_stabilization.py:739-742``: ``focus_idx.replace(0, nan).ffill().fillna(focus_idx.mean()).astype(int)``.  A 0
+    (an empty FOV, a failed estimate) takes the last estimate before it; what is still missing — the timepoints before the
+    first estimate — takes the mean, which the reference takes over the column as read: zeros count, NaN does not."""
+    v = np.asarray(list(focus_idx), dtype=np.float64)
+    mean = float(np.mean(v[~np.isnan(v)])) if (~np.isnan(v)).any() else np.nan
+    w = np.where(v == 0, np.nan, v)
+    last = np.nan
+    for i in range(len(w)):
+        if np.isnan(w[i]):
+            w[i] = last
+        else:
+            last = w[i]
+    w = np.where(np.isnan(w), mean, w)
+    if np.isnan(w).any():
+        raise ValueError("focus_idx holds no estimate to fill the missing timepoints from")
+    return [int(x) for x in w]
+
+
+def xy_transforms_from_stackreg(T_stackreg) -> np.ndarray:
+    """``estimate_stabilization.py:758-764``: the translations swapped (x, y) -> (y, x) and the 3 x 3 matrices embedded into
+    ``[1:4, 1:4]`` of 4 x 4 ZYX matrices: ``[1, 3]`` is the y shift, ``[2, 3]`` the x shift."""
+    m = np.array(T_stackreg, dtype=np.float64)
+    m[:, [0, 1], 2] = m[:, [1, 0], 2]
+    transform = np.zeros((m.shape[0], 4, 4))
+    transform[:, 1:4, 1:4] = m
+    transform[:, 0, 0] = 1
+    return transform
+
+
+def estimate_xy_stabilization_per_position(input_position_dirpath, output_folder_path, df_z_focus_path, channel_index: int,
+                                           center_crop_xy, t_reference: str = "previous", verbose: bool = False, device="cuda"):
+    """``estimate_stabilization.py:696-771``: one plane per timepoint, at its focus slice (``fill_focus_indices`` of the
+    position's rows of the focus table) and in the centre window, clipped below at 0 and registered by ``register_stack``;
+    saves ``<row>_<col>_<fov>.npy`` (float32) and returns the float64 matrices."""
+    from pathlib import Path
+
+    from .io import open_ome_zarr
+    from .stackreg import register_stack
+
+    input_position_dirpath = Path(input_position_dirpath)
+    position = str(Path(*input_position_dirpath.parts[-3:]))
+    with open_ome_zarr(input_position_dirpath) as dataset:
+        T, _, Z, Y, X = dataset.data.shape
+        ys, xs = centre_window(Y, X, center_crop_xy)
+        if verbose:
+            print(f"Reading focus index from {df_z_focus_path}")
+        z_idx = fill_focus_indices([r[3] for r in _read_focus_csv(df_z_focus_path) if r[0] == position])
+        if len(z_idx) != T:
+            raise ValueError(f"{df_z_focus_path} holds {len(z_idx)} focus indices for {position}, the position has {T} timepoints")
+        if min(z_idx) < 0 or max(z_idx) >= Z:
+            raise ValueError(f"{df_z_focus_path}: focus indices {z_idx} of {position} leave the {Z} slices of the position")
+        if verbose:
+            print("Calculating xy stabilization...")
+        tyx = np.stack([np.asarray(dataset.data[t, channel_index, z, ys, xs]) for t, z in zip(range(T), z_idx)])
+    T_stackreg = register_stack(tyx, reference=t_reference, device=device)  # the kernel reads values below 0 as 0 (:753)
+    transform = xy_transforms_from_stackreg(T_stackreg)
+    output_folder_path = Path(output_folder_path)
+    output_folder_path.mkdir(parents=True, exist_ok=True)
+    np.save(output_folder_path / f"{position.replace('/', '_')}.npy", transform.astype(np.float32))
+    return transform
+
+
+def estimate_xy_stabilization(input_position_dirpaths, output_folder_path, stack_reg_settings, channel_index: int = 0,
+                              sbatch_filepath=None, cluster: str = "local", verbose: bool = False, device="cuda") -> dict:
+    """``estimate_stabilization.py:774-897``: ``positions_focus.csv`` of the output folder is reused when it exists, otherwise
+    written by ``estimate_z_stabilization(estimate_z_index=True)`` with the nested focus settings; then every position (sharded
+    over ranks instead of submitit jobs); returns ``{<row>_<col>_<fov>: transforms}``.
+    ``stack_reg_settings``: a ``StackRegSettings``, a dict of its fields, or ``None`` for the defaults."""
+    import shutil
+    from pathlib import Path
+
+    from . import parallel
+    from .settings import StackRegSettings
+
+    s = stack_reg_settings
+    if s is None:
+        s = StackRegSettings()
+    elif isinstance(s, dict):
+        s = StackRegSettings(**s)
+    input_position_dirpaths = remove_beads_fov_from_path_list(list(input_position_dirpaths), s.skip_beads_fov)
+    output_folder_path = Path(output_folder_path)
+    output_folder_path.mkdir(parents=True, exist_ok=True)
+    df_focus_path = output_folder_path / "positions_focus.csv"
+    rank, world = parallel.init()  # binds this rank to GPU LOCAL_RANK before any device call
+    if df_focus_path.exists():
+        print("Using existing Z focus index file.")
+    else:
+        print("Estimating Z focus positions...")
+        estimate_z_stabilization(input_position_dirpaths, output_folder_path, s.focus_finding_settings, channel_index,
+                                 sbatch_filepath=sbatch_filepath, cluster=cluster, verbose=verbose, estimate_z_index=True,
+                                 device=device)
+    parallel.barrier()
+    transforms_out = output_folder_path / "xy_transforms"
+    transforms_out.mkdir(parents=True, exist_ok=True)
+    for p in parallel.shard_positions(input_position_dirpaths, rank, world):
+        estimate_xy_stabilization_per_position(p, transforms_out, df_focus_path, channel_index, s.center_crop_xy,
+                                               t_reference=s.t_reference, verbose=verbose, device=device)
+    parallel.barrier()
+    fov_transforms = {f.stem: np.load(f).tolist() for f in sorted(transforms_out.glob("*.npy"))}
+    parallel.barrier()
+    if rank == 0:
+        shutil.rmtree(transforms_out)
+    return fov_transforms
 
 
 def save_transforms(model, transforms, output_filepath_settings, output_filepath_plot=None, verbose: bool = False):

@@ -304,10 +304,19 @@ class FocusFindingSettings(_Strict):
     center_crop_xy: list[int] = [800, 800]
 
 
+class StackRegSettings(_Strict):
+    """biahub/settings.py:224-230."""
+
+    center_crop_xy: list[int] = [800, 800]
+    skip_beads_fov: str = "0"
+    focus_finding_settings: FocusFindingSettings | None = Field(default_factory=FocusFindingSettings)
+    t_reference: Literal["first", "previous"] = "first"
+
+
 class EstimateStabilizationSettings(_Strict):
-    """biahub/settings.py:295-333; ``phase-cross-corr`` (xyz), ``beads`` (xyz) and ``focus-finding`` (z) run in this package.
-    ``stack_reg_settings`` is carried as a plain dict, and so is ``focus_finding_settings``, which is validated into
-    ``FocusFindingSettings`` where it is used."""
+    """biahub/settings.py:295-333; ``phase-cross-corr`` (xyz), ``beads`` (xyz) and ``focus-finding`` (z, xy, xyz) run in this
+    package.  ``stack_reg_settings`` and ``focus_finding_settings`` are carried as plain dicts and validated into
+    ``StackRegSettings`` and ``FocusFindingSettings`` where they are used (``None``: the defaults)."""
 
     stabilization_estimation_channel: str
     stabilization_channels: list

@@ -49,6 +49,9 @@
  *                             vendor/napari_psf_analysis/psf_analysis/extract/BeadExtractor.py:36-78
  *   bh_psf_fit             <- biahub/characterize_psf.py:193-272 analyze_psf (its per-bead loop: the three curve_fit calls of
  *                             vendor/napari_psf_analysis/psf_analysis/fit/fitter.py and their initial guesses, estimator.py)
+ *   bh_stackreg_translation
+ *                          <- biahub/estimate_stabilization.py:755-756 StackReg(TRANSLATION).register_stack (pystackreg's
+ *                             TurboReg translation mode, restated: cubic-spline pyramid, Marquardt-Levenberg descent)
  *   bh_affine              <- biahub/register.py:202-281 apply_affine_transform,
  *                             biahub/stabilize.py:32-90 apply_stabilization_transform,
  *                             biahub/core/transform.py:374-396 Transform._apply_scipy
@@ -629,6 +632,42 @@ int bh_average_patches(bh_ctx* ctx, const float* in, int64_t Z, int64_t Y, int64
 int bh_psf_fit(bh_ctx* ctx, const float* in, int64_t Z, int64_t Y, int64_t X, const int* starts, const int* shapes, int n,
                const double spacing[3], double offset, double gain, int float32_math, int max_iterations, double* rows,
                double* guesses, int* status, int* iterations);
+
+/* ---- StackReg translation ------------------------------------------------------------ */
+/* Translation between n (moving, reference) pairs of frames of one device stack, TurboReg's translation mode restated in
+ * float64 (csrc/stackreg.hip).  frames: T planes of H x W of dtype (BH_DT_U8, _U16, _I16, _F32), plane t at
+ * frames + t * frame_stride, row y at + y * row_stride (strides in elements, unit stride along x), so a window of a larger
+ * resident array is read in place; values below 0 (and NaN) read as 0.  pairs: host int32[n][2], (moving, reference) frame
+ * indices.  Every frame gets a pyramid (a level is appended while min(H, W) of the last one is >= MIN_SIDE_FOR_NEXT:
+ * [1 4 6 4 1] / 16 along x, then y, whole-sample mirror boundaries, even indices kept) and cubic B-spline coefficients of
+ * every level (pole sqrt(3) - 2, mirror boundaries), built once and shared by the pairs.  Per level, coarsest first, the
+ * displacement d (doubled from the level before) descends on E(d) = mean over Omega(d) of (M(x + d) - R(x))^2 by
+ * inverse-compositional Marquardt-Levenberg steps u = (H + lambda diag H)^-1 g with the reference level's gradient images;
+ * lambda starts at LAMBDA0, is divided by LAMBDA_FACTOR when E falls strictly (the attempt d - u is kept) and multiplied
+ * otherwise; the level ends after the iteration whose |u| < EPS or after MAX_ITER.  At an integer d the moving level's values
+ * are read instead of its coefficients (the spline interpolates them), so identical frames return exactly 0.
+ * All outputs are HOST arrays:
+ *   shift_yx    n x 2   d at level 0: the moving frame's content sits at x + d where the reference's sits at x
+ *   mse         n       E at the returned d
+ *   status      n       BH_STACKREG_CONVERGED, _ITERCAP (the finest level spent MAX_ITER), _DEGENERATE: the level-0 gradient
+ *                       matrix of either frame is flat against the frame's energy (min(Hyy, Hxx) <= FLAT_REL * sum v^2), not
+ *                       finite or ill-conditioned (det <= COND_REL * Hyy Hxx), or an H of the descent is; shift and mse are 0
+ *   iterations  n       attempts, summed over the levels
+ * Working memory is 16 * (4/3) * T * H * W bytes plus 56 bytes per pair and 64 x 64 tile.  A pair's result does not depend on
+ * the other pairs of the call and is bit-reproducible (fixed tiling, fixed-order folds, no float atomics).  Synchronises. */
+#define BH_STACKREG_MIN_SIDE_FOR_NEXT 24
+#define BH_STACKREG_EPS 1e-3
+#define BH_STACKREG_MAX_ITER 20
+#define BH_STACKREG_LAMBDA0 1.0
+#define BH_STACKREG_LAMBDA_FACTOR 4.0
+#define BH_STACKREG_FLAT_REL 1e-20
+#define BH_STACKREG_COND_REL 1e-10
+#define BH_STACKREG_CONVERGED 0
+#define BH_STACKREG_ITERCAP 1
+#define BH_STACKREG_DEGENERATE 2
+int bh_stackreg_translation(bh_ctx* ctx, const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int64_t frame_stride,
+                            int64_t row_stride, const int32_t* pairs, int n, double* shift_yx, double* mse, int32_t* status,
+                            int32_t* iterations);
 
 /* ---- affine warp ------------------------------------------------------------------- */
 /* out(p) = in(M p), M = 3x4 row-major pull matrix (rows z,y,x; last column translation) in ZYX
