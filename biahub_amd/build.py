@@ -27,8 +27,8 @@ def _hipcc() -> str:
 
 # textual includes of a translation unit (rebuild triggers)
 _FC = ("fftconv.hpp", "fftconv_dev.hpp")
-INCLUDES = {"fftconv.hip": _FC + ("tune_rule.hpp",), "fftconv_col.hip": _FC, "fftconv_xtile.hip": _FC + ("fftconv_xpass.inc",), "fftconv_xw.hip": _FC + ("fftconv_xw.inc", "fftconv_x3.inc"),
-            "fftconv_colreg.hip": _FC + ("fftconv_xw.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"),
+INCLUDES = {"fftconv.hip": _FC + ("tune_rule.hpp",), "fftconv_col.hip": _FC, "fftconv_xtile.hip": _FC + ("fftconv_xpass.inc",), "fftconv_xw.hip": _FC + ("fftconv_regfft.inc", "fftconv_xrows.inc", "fftconv_xw.inc", "fftconv_x3.inc"),
+            "fftconv_colreg.hip": _FC + ("fftconv_regfft.inc", "fftconv_colw.inc", "fftconv_colz.inc", "fftconv_colz3.inc", "fftconv_zdirect.inc"),
             "deconv.hip": ("fftconv.hpp",), "invtf.hip": ("fftconv.hpp",), "affine.hip": ("affine_zwalk.inc", "affine_zoblique.inc"),
             "deskew.hip": ("deskew_geom.hpp", "deskew_rows.inc"), "host_deskew.hip": ("deskew_geom.hpp",), "lz4.hip": ("blosc_frame.hpp",),
             "zstd.hip": ("zstd_lanes.inc", "zstd_format.inc", "zstd_frame.inc", "zstd_block.inc", "blosc_frame.hpp"),

@@ -161,15 +161,15 @@ __global__ __launch_bounds__(256) void ratio_kernel(float* __restrict__ blur, co
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 b = b4[i];
         const float4 v = d4[i];
-        b.x = v.x / fmaxf(b.x, eps);
-        b.y = v.y / fmaxf(b.y, eps);
-        b.z = v.z / fmaxf(b.z, eps);
-        b.w = v.w / fmaxf(b.w, eps);
+        b.x = rl_ratio(v.x, b.x, eps);
+        b.y = rl_ratio(v.y, b.y, eps);
+        b.z = rl_ratio(v.z, b.z, eps);
+        b.w = rl_ratio(v.w, b.w, eps);
         b4[i] = b;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = n4 * 4 + threadIdx.x;
-        blur[i] = d[i] / fmaxf(blur[i], eps);
+        blur[i] = rl_ratio(d[i], blur[i], eps);
     }
 }
 
@@ -181,15 +181,15 @@ __global__ __launch_bounds__(256) void update_kernel(float* __restrict__ est, co
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         float4 e = e4[i];
         const float4 c = c4[i];
-        e.x = fmaxf(e.x * c.x, 0.0f);
-        e.y = fmaxf(e.y * c.y, 0.0f);
-        e.z = fmaxf(e.z * c.z, 0.0f);
-        e.w = fmaxf(e.w * c.w, 0.0f);
+        e.x = rl_update(e.x, c.x);
+        e.y = rl_update(e.y, c.y);
+        e.z = rl_update(e.z, c.z);
+        e.w = rl_update(e.w, c.w);
         e4[i] = e;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
         const int64_t i = n4 * 4 + threadIdx.x;
-        est[i] = fmaxf(est[i] * corr[i], 0.0f);
+        est[i] = rl_update(est[i], corr[i]);
     }
 }
 
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void fold_ratio_kernel(const float* __restrict
         const int64_t x = i % f.P[2], y = (i / f.P[2]) % f.P[1], z = i / (f.P[2] * f.P[1]);
         float r = 0.0f;
         if (z < f.N[0] && y < f.N[1] && x < f.N[2])
-            r = d[(z * f.N[1] + y) * f.N[2] + x] / fmaxf(fold_at(lin, f, z, y, x), eps);
+            r = rl_ratio(d[(z * f.N[1] + y) * f.N[2] + x], fold_at(lin, f, z, y, x), eps);
         next[i] = r;
     }
 }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void fold_update_kernel(const float* __restric
     const int64_t total = f.N[0] * f.N[1] * f.N[2];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t x = i % f.N[2], y = (i / f.N[2]) % f.N[1], z = i / (f.N[2] * f.N[1]);
-        est[i] = fmaxf(est[i] * fold_at(lin, f, z, y, x), 0.0f);
+        est[i] = rl_update(est[i], fold_at(lin, f, z, y, x));
     }
 }
 
@@ -322,8 +322,7 @@ __global__ __launch_bounds__(256) void fold_update_rewrap_kernel(const float* __
             if (plain_row && q0 >= f.hi[2] && q0 + 3 < f.N[2] - f.lo[2]) {
                 const float4 e = *reinterpret_cast<const float4*>(erow + q0);
                 const float4 c = *reinterpret_cast<const float4*>(crow0 + x);
-                *reinterpret_cast<float4*>(drow + x) = make_float4(fmaxf(e.x * c.x, 0.0f), fmaxf(e.y * c.y, 0.0f),
-                                                                    fmaxf(e.z * c.z, 0.0f), fmaxf(e.w * c.w, 0.0f));
+                *reinterpret_cast<float4*>(drow + x) = make_float4(rl_update(e.x, c.x), rl_update(e.y, c.y), rl_update(e.z, c.z), rl_update(e.w, c.w));
                 continue;
             }
             float out4[4];
@@ -343,7 +342,7 @@ __global__ __launch_bounds__(256) void fold_update_rewrap_kernel(const float* __
                             const float* crow = corr + ((int64_t)tz[a] * f.P[1] + ty[b]) * f.P[2];
                             for (int c = 0; c < nx; ++c) acc += crow[tx[c]];
                         }
-                    v = fmaxf(erow[qx] * acc, 0.0f);
+                    v = rl_update(erow[qx], acc);
                 }
                 out4[k] = v;
             }

@@ -46,6 +46,11 @@ struct ConvPlan {
 // what the inverse X pass does with the real rows it produces (fftconv_apply's `epilogue`)
 enum XEpilogue { XE_STORE = 0, XE_RATIO = 1, XE_UPDATE = 2 };
 
+// Richardson-Lucy's two pointwise steps, as every kernel that applies them (X-pass epilogues, deconv.hip) computes them:
+// a true divide, and a product that is rounded before the clamp
+__device__ __forceinline__ float rl_ratio(float d, float blur, float eps) { return d / fmaxf(blur, eps); }
+__device__ __forceinline__ float rl_update(float est, float corr) { return fmaxf(est * corr, 0.0f); }
+
 // ---- shapes and plans ----
 bool fftconv_supported(int64_t Z, int64_t Y, int64_t X);
 bool fftconv_supported_ex(int64_t Z, int64_t Y, int64_t X, bool radix3);

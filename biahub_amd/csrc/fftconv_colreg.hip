@@ -5,7 +5,7 @@
 
 namespace bh {
 
-#include "fftconv_xw.inc"  // the in-register butterflies (xw::reg_fft) and xw::opaque_i
+#include "fftconv_regfft.inc"  // the in-register butterflies (xw::reg_fft), xw::brev_c and xw::opaque_i
 #include "fftconv_colw.inc"
 #include "fftconv_colz.inc"
 #include "fftconv_colz3.inc"

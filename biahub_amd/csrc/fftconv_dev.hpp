@@ -60,7 +60,7 @@ __device__ __forceinline__ cf cmulc(cf a, cf b) {  // a * conj(b)
 }
 // a - i b and a + i b as ONE packed add each: v_pk_add_f32 takes either half of each source for each half of the result and can
 // negate it.  The compiler's own lowering materialises (-i) b with two moves first — a fifth of the register FFT stages'
-// instructions were such moves (fftconv_xw.inc reg_fft, fftconv_colz.inc fwd8p / inv8p fold every rotation by -i / +i into
+// instructions were such moves (fftconv_regfft.inc reg_fft, fftconv_colz.inc fwd8p / inv8p fold every rotation by -i / +i into
 // the add or subtract that consumes it).
 __host__ __device__ __forceinline__ cf add_mi(cf a, cf b) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -478,11 +478,11 @@ struct XParams {
     float eps;
 };
 
-// modes and parameters of the wave-private X passes (kernels: fftconv_xw.inc, fftconv_x3.inc); here because the drivers of
-// fftconv.hip name the modes and build the wrap geometry
+// modes and parameters of the wave-private X passes (kernels: fftconv_xw.inc, fftconv_x3.inc; what a mode implies:
+// ModeOf in fftconv_xrows.inc); here because the drivers of fftconv.hip name the modes and build the wrap geometry
 namespace xw {
 
-// the _WRAP modes (fftconv_x3.inc only): Richardson-Lucy at a wrap-padded box without a fold pass — the epilogue's result is
+// the _WRAP modes (both kernel families): Richardson-Lucy at a wrap-padded box without a fold pass — the epilogue's result is
 // wrap-extended along x inside the row and along z by re-reading the source plane, out of place (Params::S_out, Params::wz / wx)
 // INV_UPDATE_CROP: the last update of that loop — max(est * ., 0) stored straight into the UNPADDED output volume (rows of
 // wx.n floats at any 4-byte alignment; planes / columns outside the volume are not stored): no crop pass

@@ -1,5 +1,7 @@
 // Radix-3 wave-private X passes of the fused FFT engine: rows of 1536 or 3072 voxels (packed complex transforms of
-// M = 3 L points, L = 256 or 512) — included by fftconv_xw.hip after fftconv_xw.inc, whose helpers it shares.
+// M = 3 L points, L = 256 or 512) — included by fftconv_xw.hip after fftconv_regfft.inc (the in-register butterflies) and
+// fftconv_xrows.inc (the row-pair frame shared with fftconv_xw.inc: mode predicates, the rows of a pair, access addresses,
+// Richardson-Lucy's value step).
 //
 // A deskewed volume never has power-of-two rows: the wrap-padded engine box of BASELINE config 4's (342, 1024, 1517) volume is
 // (384, 1024, 1536), that of config 2's (683, 2048, 3034) is (768, 2048, 3072).  Those rows used to take the tile kernels of
@@ -25,23 +27,9 @@
 // tables, untangle pairing, stored column order), checked against numpy's FFT in the CPU suite.
 namespace x3 {
 
-using xw::brev_c;
-using xw::Mode;
-using xw::mulw16;
-using xw::opaque_i;
-using xw::pack2;
-using xw::Params;
-using xw::parity;
-using xw::xw_fence;
-using xw::FUSED_RATIO;
-using xw::FUSED_RATIO_WRAP;
-using xw::FUSED_UPDATE;
-using xw::FUSED_UPDATE_WRAP;
-using xw::FWD;
-using xw::INV_RATIO;
-using xw::INV_STORE;
-using xw::INV_UPDATE;
-using xw::INV_UPDATE_CROP;
+// modes, parameters, the butterflies of fftconv_regfft.inc and the row-pair frame of fftconv_xrows.inc; what this file
+// declares under the same name as fftconv_xw.inc (Geo, LaneAddr, swz, reg_fft, untangle, ...) hides that one here
+using namespace xw;
 
 #ifndef BH_X3_NW
 #define BH_X3_NW 4  // wavefronts per workgroup (one workgroup per CU): 6 row buffers of 4.5 KiB per pair leave room for 4-5
@@ -304,13 +292,7 @@ __device__ __forceinline__ void untangle(cf (&x)[24], const cf (&w0)[8], const c
 template <int LOGL, int MODE>
 __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
     using G = Geo<LOGL>;
-    constexpr bool WRAP = MODE == FUSED_RATIO_WRAP || MODE == FUSED_UPDATE_WRAP;
-    constexpr bool HAS_INV = MODE != FWD;
-    constexpr bool HAS_FWD = MODE == FWD || MODE == FUSED_RATIO || MODE == FUSED_UPDATE || WRAP;
-    constexpr bool RATIO = MODE == INV_RATIO || MODE == FUSED_RATIO || MODE == FUSED_RATIO_WRAP;
-    constexpr bool CROP = MODE == INV_UPDATE_CROP;  // the last update, stored straight into the unpadded output volume
-    constexpr bool UPDATE = MODE == INV_UPDATE || MODE == FUSED_UPDATE || MODE == FUSED_UPDATE_WRAP || CROP;
-    constexpr bool STORE_REAL = MODE != FUSED_RATIO && MODE != FUSED_RATIO_WRAP;  // the ratio of a fused pass never leaves the chip
+    using MD = ModeOf<MODE>;
     constexpr int M = G::M, LG = G::LG, X = 2 * M, L = G::L;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     cf* tab = reinterpret_cast<cf*>(smem);
@@ -334,45 +316,7 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
     const int pstep = (int)gridDim.x * NW * G::PAIRS;
     const int laneS = grp * XP * 8 + l * 16;  // byte offset into a spectrum row pair
     const int laneR = grp * X * 4 + l * 8;    // byte offset into a real row pair
-    struct Rows {
-        long ra, rb;    // the pair's rows: where results go
-        long sa_, sb_;  // the rows read (WRAP: those of the plane this plane mirrors)
-        int yy;
-        bool zero;      // WRAP: a plane beyond the wrap margins holds zeros
-    };
-    cf* const Sdst = WRAP ? p.S_out : p.S;
-    auto rows_of = [&](int pb) {
-        Rows r;
-        const int z = pb / Yh;
-        r.yy = pb - z * Yh;
-        r.ra = (long)z * p.Y + r.yy;
-        r.rb = r.ra + Yh;
-        r.sa_ = r.ra;
-        r.sb_ = r.rb;
-        r.zero = false;
-        if (WRAP) {
-            int rel = z - p.wz.off;
-            if (rel >= p.wz.n + p.wz.mhi) rel -= p.Z;
-            r.zero = rel < -p.wz.mlo || rel >= p.wz.n + p.wz.mhi;
-            rel += rel < 0 ? p.wz.n : (rel >= p.wz.n ? -p.wz.n : 0);
-            const int zs = r.zero ? z : rel + p.wz.off;
-            r.sa_ = (long)zs * p.Y + r.yy;
-            r.sb_ = r.sa_ + Yh;
-        }
-        return r;
-    };
-    auto at4 = [](const void* base, long row, int pitch_bytes, int lane_off, int imm) {
-        return reinterpret_cast<const float4*>(static_cast<const unsigned char*>(base) + row * pitch_bytes + (lane_off + imm));
-    };
-    auto at4_w = [](void* base, long row, int pitch_bytes, int lane_off, int imm) {
-        return reinterpret_cast<float4*>(static_cast<unsigned char*>(base) + row * pitch_bytes + (lane_off + imm));
-    };
-    auto at2 = [](const void* base, long row, int pitch_bytes, int lane_off, int imm) {
-        return reinterpret_cast<const float2*>(static_cast<const unsigned char*>(base) + row * pitch_bytes + (lane_off + imm));
-    };
-    auto at2_w = [](void* base, long row, int pitch_bytes, int lane_off, int imm) {
-        return reinterpret_cast<float2*>(static_cast<unsigned char*>(base) + row * pitch_bytes + (lane_off + imm));
-    };
+    cf* const Sdst = MD::WRAP ? p.S_out : p.S;
     // real-side element (third t, register rho) = complex index t L + rho BLK + l: byte offset in the row beyond laneR
     auto imm_r = [](int i) { return ((i >> 3) * L + (i & 7) * G::BLK) * 8; };
 
@@ -382,20 +326,20 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
     float2 ra_[24], rb_[24];
     cf nya = make_float2(0.f, 0.f), nyb = nya;
     auto load_pair = [&](int pb) {
-        const Rows r = rows_of(pb);
-        if (HAS_INV) {
+        const Rows r = rows_of<MD::WRAP>(p, pb, Yh);
+        if (MD::HAS_INV) {
 #pragma unroll
             for (int c = 0; c < 12; ++c) {
-                sa[c] = *at4(p.S, r.sa_, XP * 8, laneS, c * LG * 16);
-                sb[c] = *at4(p.S, r.sb_, XP * 8, laneS, c * LG * 16);
+                sa[c] = *at<float4>(p.S, r.sa_, XP * 8, laneS, c * LG * 16);
+                sb[c] = *at<float4>(p.S, r.sb_, XP * 8, laneS, c * LG * 16);
             }
             nya = *reinterpret_cast<const cf*>(reinterpret_cast<const unsigned char*>(p.S) + r.sa_ * XP * 8 + (grp * XP * 8 + M * 8));
             nyb = *reinterpret_cast<const cf*>(reinterpret_cast<const unsigned char*>(p.S) + r.sb_ * XP * 8 + (grp * XP * 8 + M * 8));
         } else {
 #pragma unroll
             for (int i = 0; i < 24; ++i) {
-                ra_[i] = *at2(p.in, r.ra, X * 4, laneR, imm_r(i));
-                rb_[i] = *at2(p.in, r.rb, X * 4, laneR, imm_r(i));
+                ra_[i] = *at<float2>(p.in, r.ra, X * 4, laneR, imm_r(i));
+                rb_[i] = *at<float2>(p.in, r.rb, X * 4, laneR, imm_r(i));
             }
         }
     };
@@ -409,7 +353,7 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
         a.dc_c4[0] = opaque_i(a.dc_c4[0]);
         a.dc_c4[1] = opaque_i(a.dc_c4[1]);
         a.dc_c4[2] = opaque_i(a.dc_c4[2]);
-        const Rows rw = rows_of(pb);
+        const Rows rw = rows_of<MD::WRAP>(p, pb, Yh);
         const cf wy = p.twy[rw.yy + grp];
         const int pnext = pb + pstep < npairs ? pb + pstep : pb;  // unconditional prefetch: the last round re-reads its own pair
         cf xa[24], xb[24];
@@ -432,7 +376,7 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
             xw_fence();
         };
 
-        if (HAS_INV) {
+        if (MD::HAS_INV) {
 #pragma unroll
             for (int c = 0; c < 12; ++c) {
                 xa[2 * c] = make_float2(sa[c].x, sa[c].y);
@@ -497,19 +441,19 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
             xw_fence();
             // this pair's d / est rows ride behind the last inverse stage
             float2 auxa[24], auxb[24];
-            if (RATIO || UPDATE) {
+            if (MD::RATIO || MD::UPDATE) {
 #pragma unroll
-                for (int i = 0; i < 24; ++i) auxa[i] = *at2(p.aux, rw.sa_, X * 4, laneR, imm_r(i));
+                for (int i = 0; i < 24; ++i) auxa[i] = *at<float2>(p.aux, rw.sa_, X * 4, laneR, imm_r(i));
 #pragma unroll
-                for (int i = 0; i < 24; ++i) auxb[i] = *at2(p.aux, rw.sb_, X * 4, laneR, imm_r(i));
+                for (int i = 0; i < 24; ++i) auxb[i] = *at<float2>(p.aux, rw.sb_, X * 4, laneR, imm_r(i));
             }
             // ---- last inverse stage, inverse radix-3 and epilogue, one row at a time; a fused pass sends the row straight on
             // into the first half of its forward transform (the row's LDS buffers are free again once it is in registers) ----
             const bool zero_plane = rw.zero;
             auto tail_row = [&](cf (&x)[24], const float2 (&aux)[24], unsigned char* buf, long row) {
                 // CROP: this row's plane and row inside the unpadded output volume (64-bit division once per row, not per store)
-                const int zq = CROP ? (int)(row / p.Y) - p.wz.off : 0;
-                const long yq = CROP ? row % p.Y + grp : 0;
+                const int zq = MD::CROP ? (int)(row / p.Y) - p.wz.off : 0;
+                const long yq = MD::CROP ? row % p.Y + grp : 0;
                 get_da<LOGL>(buf, x, a, 0);
                 get_da<LOGL>(buf, x, a, 1);
                 get_da<LOGL>(buf, x, a, 2);
@@ -521,14 +465,8 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
 #pragma unroll
                 for (int i = 0; i < 24; ++i) {
                     float2 v = x[i];
-                    if (RATIO) {
-                        v.x = aux[i].x / fmaxf(v.x, p.eps);
-                        v.y = aux[i].y / fmaxf(v.y, p.eps);
-                    } else if (UPDATE) {
-                        v.x = fmaxf(aux[i].x * v.x, 0.0f);
-                        v.y = fmaxf(aux[i].y * v.y, 0.0f);
-                    }
-                    if (CROP) {
+                    if (MD::RATIO || MD::UPDATE) v = value_op<MODE>(v, aux[i], p.eps);
+                    if (MD::CROP) {
                         const int xq = 2 * ((i >> 3) * L + (i & 7) * G::BLK + l) - p.wx.off;
                         if (zq >= 0 && zq < p.wz.n) {
                             float* dst = p.out + ((long)zq * p.Y + yq) * p.wx.n + xq;
@@ -540,10 +478,10 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
                                 if (xq + 1 >= 0 && xq + 1 < p.wx.n) dst[1] = v.y;
                             }
                         }
-                    } else if (STORE_REAL && !WRAP) *at2_w(p.out, row, X * 4, laneR, imm_r(i)) = v;
+                    } else if (MD::STORE_REAL && !MD::WRAP) *at_w<float2>(p.out, row, X * 4, laneR, imm_r(i)) = v;
                     x[i] = v;
                 }
-                if (WRAP) {
+                if (MD::WRAP) {
                     // Wrap-extension along x inside the row.  The epilogue's values are right on the volume's own voxels
                     // (box positions [off, off + n)); margin position rel = pos - off in [-mlo, 0) takes the value of voxel
                     // rel + n, rel in [n, n + mhi) that of voxel rel - n, everything else is zero.  The two source strips
@@ -585,16 +523,16 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
                         for (int i = 0; i < 24; ++i) x[i] = make_float2(0.f, 0.f);
                     }
                     xw_fence();  // the scratch strips are read before the forward transform overwrites them
-                    if (STORE_REAL) {
+                    if (MD::STORE_REAL) {
 #pragma unroll
-                        for (int i = 0; i < 24; ++i) *at2_w(p.out, row, X * 4, laneR, imm_r(i)) = x[i];
+                        for (int i = 0; i < 24; ++i) *at_w<float2>(p.out, row, X * 4, laneR, imm_r(i)) = x[i];
                     }
                 }
-                if (HAS_FWD) fwd_row_head(x, buf);
+                if (MD::HAS_FWD) fwd_row_head(x, buf);
             };
             tail_row(xa, auxa, ba, rw.ra);
             tail_row(xb, auxb, bb, rw.rb);
-            if (MODE == INV_RATIO || MODE == INV_UPDATE || CROP) load_pair(pnext);
+            if (MODE == INV_RATIO || MODE == INV_UPDATE || MD::CROP) load_pair(pnext);
         } else {
 #pragma unroll
             for (int i = 0; i < 24; ++i) {
@@ -613,8 +551,8 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
                 for (int i = 0; i < 24; ++i) {
                     xa[i] = make_float2(fmaxf(xa[i].x, 0.f), fmaxf(xa[i].y, 0.f));
                     xb[i] = make_float2(fmaxf(xb[i].x, 0.f), fmaxf(xb[i].y, 0.f));
-                    *at2_w(p.out, rw.ra, X * 4, laneR, imm_r(i)) = xa[i];
-                    *at2_w(p.out, rw.rb, X * 4, laneR, imm_r(i)) = xb[i];
+                    *at_w<float2>(p.out, rw.ra, X * 4, laneR, imm_r(i)) = xa[i];
+                    *at_w<float2>(p.out, rw.rb, X * 4, laneR, imm_r(i)) = xb[i];
                 }
             }
             xw_fence();
@@ -623,8 +561,8 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
             fwd_row_head(xa, ba);
             fwd_row_head(xb, bb);
         }
-        if (HAS_FWD) {
-            if (HAS_INV) {
+        if (MD::HAS_FWD) {
+            if (MD::HAS_INV) {
                 xw_fence();
                 load_pair(pnext);  // the next pair's spectrum rows ride behind the rest of the forward transform
                 xw_fence();
@@ -684,8 +622,8 @@ __global__ __launch_bounds__(NT) void x3_kernel(Params p) {
             const cf nyA = make_float2(na + nb, 0.f), nyB = cmul(make_float2(na - nb, 0.f), wy);
 #pragma unroll
             for (int c = 0; c < 12; ++c) {
-                *at4_w(Sdst, rw.ra, XP * 8, laneS, c * LG * 16) = pack2(xa[2 * c], xa[2 * c + 1]);
-                *at4_w(Sdst, rw.rb, XP * 8, laneS, c * LG * 16) = pack2(xb[2 * c], xb[2 * c + 1]);
+                *at_w<float4>(Sdst, rw.ra, XP * 8, laneS, c * LG * 16) = pack2(xa[2 * c], xa[2 * c + 1]);
+                *at_w<float4>(Sdst, rw.rb, XP * 8, laneS, c * LG * 16) = pack2(xb[2 * c], xb[2 * c + 1]);
             }
             if (l < 16) {  // Nyquist column (lane 0) + the zero pad columns of the row pitch
                 const cf zero = make_float2(0.f, 0.f);

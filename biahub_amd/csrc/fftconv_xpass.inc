@@ -338,16 +338,16 @@ __global__ __launch_bounds__(FC_XNT) void x_inv_kernel(XParams p) {
             float4 r = make_float4(e0.x, e0.y, e1.x, e1.y);
             if (EPI == XE_RATIO) {
                 const float4 dd = aux[u];
-                r.x = dd.x / fmaxf(r.x, p.eps);
-                r.y = dd.y / fmaxf(r.y, p.eps);
-                r.z = dd.z / fmaxf(r.z, p.eps);
-                r.w = dd.w / fmaxf(r.w, p.eps);
+                r.x = rl_ratio(dd.x, r.x, p.eps);
+                r.y = rl_ratio(dd.y, r.y, p.eps);
+                r.z = rl_ratio(dd.z, r.z, p.eps);
+                r.w = rl_ratio(dd.w, r.w, p.eps);
             } else if (EPI == XE_UPDATE) {
                 const float4 e = aux[u];
-                r.x = fmaxf(e.x * r.x, 0.0f);
-                r.y = fmaxf(e.y * r.y, 0.0f);
-                r.z = fmaxf(e.z * r.z, 0.0f);
-                r.w = fmaxf(e.w * r.w, 0.0f);
+                r.x = rl_update(e.x, r.x);
+                r.y = rl_update(e.y, r.y);
+                r.z = rl_update(e.z, r.z);
+                r.w = rl_update(e.w, r.w);
             }
             // the ratio of a fused pass never leaves the chip; everything else is written out
             if (mine && !(FUSE && EPI == XE_RATIO))

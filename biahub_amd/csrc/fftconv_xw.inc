@@ -1,4 +1,6 @@
-// Wave-private X passes of the fused FFT engine (rows of 1024 or 2048 voxels) — included by fftconv_xw.hip (and by fftconv_colreg.hip for its in-register butterflies).
+// Wave-private X passes of the fused FFT engine (rows of 512, 1024 or 2048 voxels) — included by fftconv_xw.hip after
+// fftconv_regfft.inc (the in-register butterflies) and fftconv_xrows.inc (the row-pair frame shared with fftconv_x3.inc: mode
+// predicates, the rows of a pair, access addresses, Richardson-Lucy's value step).
 //
 // The tile-based X passes (fftconv_xpass.inc) keep 16 rows in one LDS tile and run every radix-4 step as an LDS round trip
 // with a workgroup barrier: 14 round trips per fused pass, LDS- and barrier-bound at 38-50 % of the HBM rate
@@ -42,11 +44,6 @@ struct Geo {
     static constexpr size_t LDS_BYTES = ((size_t)NTAB + (size_t)NW * PAIRS * 2 * ROWWORDS) * 8;
 };
 
-__host__ __device__ constexpr int parity(int v) {
-    int p = 0;
-    for (int b = 0; b < 16; ++b) p ^= (v >> b) & 1;
-    return p;
-}
 // XOR swizzle of the four 16-B chunks of an 8-point group (tools/xw_model.py: `swz`)
 __host__ __device__ constexpr int swz(int g) { return parity(g & 6) | (parity(g & 59) << 1); }
 
@@ -91,182 +88,6 @@ __host__ __device__ __forceinline__ int idx_d2(int l, int rho) {  // middle stag
 template <int LOGM>
 __host__ __device__ __forceinline__ int idx_d3(int l, int rho) {  // spectrum end: rho = 8 sigma + n
     return 8 * group_of_dev(l, rho >> 3) + (rho & 7);
-}
-
-__host__ __device__ __forceinline__ void xw_fence() {
-    // LDS operations of one wavefront execute in order; this only pins the compiler's schedule around an exchange
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_wave_barrier();
-#endif
-    asm volatile("" ::: "memory");
-}
-
-// d * exp(-/+ 2 pi i k / 16), k in [0, 8) a compile-time constant after unrolling
-template <bool INV>
-__host__ __device__ __forceinline__ cf mulw16(cf d, int k) {
-    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R = 0.70710678118654752f;
-    switch (k) {
-        case 0: return d;
-        case 4: return INV ? mul_pi(d) : mul_mi(d);
-        case 2: return INV ? make_float2((d.x - d.y) * R, (d.x + d.y) * R) : make_float2((d.x + d.y) * R, (d.y - d.x) * R);
-        case 6: return INV ? make_float2((-d.x - d.y) * R, (d.x - d.y) * R) : make_float2((d.y - d.x) * R, (-d.x - d.y) * R);
-        default: {
-            const float c = k == 1 ? C1 : (k == 3 ? S1 : (k == 5 ? -S1 : -C1));
-            const float s = (k == 1 || k == 7) ? S1 : C1;
-            return INV ? make_float2(d.x * c - d.y * s, d.x * s + d.y * c) : make_float2(d.x * c + d.y * s, d.y * c - d.x * s);
-        }
-    }
-}
-
-// in-register radix-2^LOGR transform of x[BASE + i * STRIDE], i < 2^LOGR.  Forward: decimation in frequency, natural in ->
-// bit-reversed out; inverse: the mirrored decimation in time with conjugate twiddles, bit-reversed in -> natural out.
-// reg_fft_levels is the definition (radix-2 levels with the rotations w_16^k applied one by one); reg_fft (BH_XW_PKROT, default)
-// computes the same values with every rotation by -i / +i folded into the packed add / subtract that consumes it (add_mi /
-// add_pi: one instruction instead of two moves and an add) and the eighth roots as (1 -+ i) R: the order of the outputs is
-// unchanged, the results agree to rounding (tools/xw_model.py checks the algebra).
-#ifndef BH_XW_PKROT
-#define BH_XW_PKROT 1
-#endif
-template <int LOGR, int BASE, int STRIDE, bool INV, int NX>
-__host__ __device__ __forceinline__ void reg_fft_levels(cf (&x)[NX]) {
-    constexpr int R = 1 << LOGR;
-    if (!INV) {
-#pragma unroll
-        for (int lh = LOGR - 1; lh >= 0; --lh) {
-            const int h = 1 << lh;
-#pragma unroll
-            for (int blk = 0; blk < R; blk += 2 * h) {
-#pragma unroll
-                for (int j = 0; j < h; ++j) {
-                    const int ia = BASE + (blk + j) * STRIDE, ib = BASE + (blk + j + h) * STRIDE;
-                    const cf a = x[ia], b = x[ib];
-                    x[ia] = cadd(a, b);
-                    x[ib] = mulw16<false>(csub(a, b), j * (8 / h));
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int lh = 0; lh < LOGR; ++lh) {
-            const int h = 1 << lh;
-#pragma unroll
-            for (int blk = 0; blk < R; blk += 2 * h) {
-#pragma unroll
-                for (int j = 0; j < h; ++j) {
-                    const int ia = BASE + (blk + j) * STRIDE, ib = BASE + (blk + j + h) * STRIDE;
-                    const cf a = x[ia], b = mulw16<true>(x[ib], j * (8 / h));
-                    x[ia] = cadd(a, b);
-                    x[ib] = csub(a, b);
-                }
-            }
-        }
-    }
-}
-
-constexpr float RQ = 0.70710678118654752f;
-// radix-4 / radix-8 butterflies on four / eight values; ROT: the upper half of the inputs carries a pending factor -i
-template <bool ROT>
-__host__ __device__ __forceinline__ void r4_dif(cf& x0, cf& x1, cf& x2, cf& x3) {
-    const cf s0 = ROT ? add_mi(x0, x2) : cadd(x0, x2), d0 = ROT ? add_pi(x0, x2) : csub(x0, x2);
-    const cf s1 = ROT ? add_mi(x1, x3) : cadd(x1, x3), d1 = ROT ? add_pi(x1, x3) : csub(x1, x3);
-    x0 = cadd(s0, s1);
-    x1 = csub(s0, s1);
-    x2 = add_mi(d0, d1);
-    x3 = add_pi(d0, d1);
-}
-template <bool ROT>
-__host__ __device__ __forceinline__ void r8_dif(cf& x0, cf& x1, cf& x2, cf& x3, cf& x4, cf& x5, cf& x6, cf& x7) {
-    cf s0 = ROT ? add_mi(x0, x4) : cadd(x0, x4), d0 = ROT ? add_pi(x0, x4) : csub(x0, x4);
-    cf s1 = ROT ? add_mi(x1, x5) : cadd(x1, x5), d1 = ROT ? add_pi(x1, x5) : csub(x1, x5);
-    cf s2 = ROT ? add_mi(x2, x6) : cadd(x2, x6), d2 = ROT ? add_pi(x2, x6) : csub(x2, x6);
-    cf s3 = ROT ? add_mi(x3, x7) : cadd(x3, x7), d3 = ROT ? add_pi(x3, x7) : csub(x3, x7);
-    r4_dif<false>(s0, s1, s2, s3);
-    cf f1 = cscale(add_mi(d1, d1), RQ), f3 = cscale(add_mi(d3, d3), RQ);  // w_8^1 d1, and i w_8^3 d3
-    r4_dif<true>(d0, f1, d2, f3);
-    x0 = s0, x1 = s1, x2 = s2, x3 = s3, x4 = d0, x5 = f1, x6 = d2, x7 = f3;
-}
-__host__ __device__ __forceinline__ void r4_dit(cf& x0, cf& x1, cf& x2, cf& x3) {
-    const cf p0 = cadd(x0, x1), q0 = csub(x0, x1), p1 = cadd(x2, x3), q1 = csub(x2, x3);
-    x0 = cadd(p0, p1);
-    x1 = add_pi(q0, q1);
-    x2 = csub(p0, p1);
-    x3 = add_mi(q0, q1);
-}
-__host__ __device__ __forceinline__ void r8_dit(cf& x0, cf& x1, cf& x2, cf& x3, cf& x4, cf& x5, cf& x6, cf& x7) {
-    r4_dit(x0, x1, x2, x3);
-    r4_dit(x4, x5, x6, x7);
-    const cf y1 = cscale(add_pi(x5, x5), RQ), e3 = cscale(add_pi(x7, x7), RQ);  // conj(w_8^1) x5, and -i conj(w_8^3) x7
-    const cf u0 = x0, u1 = x1, u2 = x2, u3 = x3, v0 = x4, v2 = x6;
-    x0 = cadd(u0, v0);
-    x4 = csub(u0, v0);
-    x1 = cadd(u1, y1);
-    x5 = csub(u1, y1);
-    x2 = add_pi(u2, v2);
-    x6 = add_mi(u2, v2);
-    x3 = add_pi(u3, e3);
-    x7 = add_mi(u3, e3);
-}
-
-template <int LOGR, int BASE, int STRIDE, bool INV, int NX>
-__host__ __device__ __forceinline__ void reg_fft(cf (&x)[NX]) {  // NX = 16 (fftconv_xw.inc, fftconv_colw.inc) or 24 (fftconv_x3.inc)
-#define BH_X(i) x[BASE + (i) * STRIDE]
-    if constexpr (!BH_XW_PKROT || LOGR < 2 || LOGR > 4) {
-        reg_fft_levels<LOGR, BASE, STRIDE, INV, NX>(x);
-    } else if constexpr (LOGR == 2) {
-        if constexpr (!INV) r4_dif<false>(BH_X(0), BH_X(1), BH_X(2), BH_X(3));
-        else r4_dit(BH_X(0), BH_X(1), BH_X(2), BH_X(3));
-    } else if constexpr (LOGR == 3) {
-        if constexpr (!INV) r8_dif<false>(BH_X(0), BH_X(1), BH_X(2), BH_X(3), BH_X(4), BH_X(5), BH_X(6), BH_X(7));
-        else r8_dit(BH_X(0), BH_X(1), BH_X(2), BH_X(3), BH_X(4), BH_X(5), BH_X(6), BH_X(7));
-    } else if constexpr (!INV) {
-        // radix 16, forward: sums -> radix 8; differences d_j w_16^j -> radix 8 whose upper four inputs carry -i (w_16^(j+4) = -i w_16^j)
-        cf d[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const cf a = BH_X(j), b = BH_X(j + 8);
-            BH_X(j) = cadd(a, b);
-            d[j] = csub(a, b);
-        }
-        r8_dif<false>(BH_X(0), BH_X(1), BH_X(2), BH_X(3), BH_X(4), BH_X(5), BH_X(6), BH_X(7));
-        d[1] = mulw16<false>(d[1], 1);
-        d[5] = mulw16<false>(d[5], 1);
-        d[2] = cscale(add_mi(d[2], d[2]), RQ);
-        d[6] = cscale(add_mi(d[6], d[6]), RQ);
-        d[3] = mulw16<false>(d[3], 3);
-        d[7] = mulw16<false>(d[7], 3);
-        r8_dif<true>(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) BH_X(j + 8) = d[j];
-    } else {
-        // radix 16, inverse: two radix-8 halves, then the upper one times conj(w_16^j), its elements 4..7 with the extra +i folded
-        r8_dit(BH_X(0), BH_X(1), BH_X(2), BH_X(3), BH_X(4), BH_X(5), BH_X(6), BH_X(7));
-        r8_dit(BH_X(8), BH_X(9), BH_X(10), BH_X(11), BH_X(12), BH_X(13), BH_X(14), BH_X(15));
-        cf v[8];
-        v[0] = BH_X(8);
-        v[4] = BH_X(12);
-        v[1] = mulw16<true>(BH_X(9), 1);
-        v[5] = mulw16<true>(BH_X(13), 1);
-        v[2] = cscale(add_pi(BH_X(10), BH_X(10)), RQ);
-        v[6] = cscale(add_pi(BH_X(14), BH_X(14)), RQ);
-        v[3] = mulw16<true>(BH_X(11), 3);
-        v[7] = mulw16<true>(BH_X(15), 3);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const cf l = BH_X(j), l4 = BH_X(j + 4);
-            BH_X(j) = cadd(l, v[j]);
-            BH_X(j + 8) = csub(l, v[j]);
-            BH_X(j + 4) = add_pi(l4, v[j + 4]);
-            BH_X(j + 12) = add_mi(l4, v[j + 4]);
-        }
-    }
-#undef BH_X
-}
-
-__host__ __device__ constexpr int brev_c(int v, int bits) {
-    int r = 0;
-    for (int b = 0; b < bits; ++b)
-        if (v >> b & 1) r |= 1 << (bits - 1 - b);
-    return r;
 }
 
 // ---- the three stages on the 16 registers of one row; `tw` tables live in LDS ----
@@ -404,7 +225,6 @@ __host__ __device__ __forceinline__ int off_d3(const LaneAddr& a, int c) {  // 1
     return a.d3_base[c >> 2] + (((c & 3) << 4) ^ a.d3_c4[c >> 2]);
 }
 
-__host__ __device__ __forceinline__ float4 pack2(cf a, cf b) { return make_float4(a.x, a.y, b.x, b.y); }
 template <int LOGM>
 __host__ __device__ __forceinline__ void put_dr(unsigned char* buf, const cf (&x)[16], const LaneAddr& a) {
 #pragma unroll
@@ -579,22 +399,10 @@ __host__ __device__ __forceinline__ void pair_fwd_tail(cf (&xa)[16], cf (&xb)[16
     nyB = cmul(make_float2(na - nb, 0.f), wy);
 }
 
-__device__ __forceinline__ int opaque_i(int v) {
-    asm volatile("" : "+v"(v));  // the value looks loop-variant: address arithmetic built on it is not hoisted into registers
-    return v;
-}
-
 template <int LOGM, int MODE>
 __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
     using G = Geo<LOGM>;
-    constexpr bool WRAP = MODE == FUSED_RATIO_WRAP || MODE == FUSED_UPDATE_WRAP;  // see fftconv_x3.inc / fftconv_richardson_lucy_wrap
-    constexpr bool HAS_INV = MODE != FWD;
-    constexpr bool HAS_FWD = MODE == FWD || MODE == FUSED_RATIO || MODE == FUSED_UPDATE || WRAP;
-    constexpr bool RATIO = MODE == INV_RATIO || MODE == FUSED_RATIO || MODE == FUSED_RATIO_WRAP;
-    constexpr bool CROP = MODE == INV_UPDATE_CROP;
-    constexpr bool UPDATE = MODE == INV_UPDATE || MODE == FUSED_UPDATE || MODE == FUSED_UPDATE_WRAP || CROP;
-    constexpr bool ARGMAX = MODE == INV_ARGMAX;
-    constexpr bool STORE_REAL = MODE != FUSED_RATIO && MODE != FUSED_RATIO_WRAP && !ARGMAX;  // the ratio of a fused pass never leaves the chip
+    using MD = ModeOf<MODE>;
     constexpr int M = G::M, LG = G::LG, X = 2 * M;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     cf* tab = reinterpret_cast<cf*>(smem);
@@ -618,58 +426,26 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
     // a wavefront's PAIRS row pairs are neighbours in y (Yh is a multiple of PAIRS): rows ra0 + grp and rb0 + grp
     const int laneS = grp * XP * 8 + l * 16;        // byte offset into a spectrum row pair
     const int laneR = grp * X * 4 + l * 16;         // byte offset into a real row pair
-    struct Rows {
-        long ra, rb;    // first row of the wavefront's pairs (uniform): where results go
-        long sa_, sb_;  // the rows read (WRAP: those of the plane this plane mirrors)
-        int yy;
-        bool zero;      // WRAP: a plane beyond the wrap margins holds zeros
-    };
-    cf* const Sdst = WRAP ? p.S_out : p.S;
-    auto rows_of = [&](int pb) {
-        Rows r;
-        const int z = pb / Yh;
-        r.yy = pb - z * Yh;
-        r.ra = (long)z * p.Y + r.yy;
-        r.rb = r.ra + Yh;
-        r.sa_ = r.ra;
-        r.sb_ = r.rb;
-        r.zero = false;
-        if (WRAP) {
-            int rel = z - p.wz.off;
-            if (rel >= p.wz.n + p.wz.mhi) rel -= p.Z;
-            r.zero = rel < -p.wz.mlo || rel >= p.wz.n + p.wz.mhi;
-            rel += rel < 0 ? p.wz.n : (rel >= p.wz.n ? -p.wz.n : 0);
-            const int zs = r.zero ? z : rel + p.wz.off;
-            r.sa_ = (long)zs * p.Y + r.yy;
-            r.sb_ = r.sa_ + Yh;
-        }
-        return r;
-    };
-    auto at = [](const void* base, long row, int pitch_bytes, int lane_off, int imm) {
-        return reinterpret_cast<const float4*>(static_cast<const unsigned char*>(base) + row * pitch_bytes + (lane_off + imm));
-    };
-    auto at_w = [](void* base, long row, int pitch_bytes, int lane_off, int imm) {
-        return reinterpret_cast<float4*>(static_cast<unsigned char*>(base) + row * pitch_bytes + (lane_off + imm));
-    };
+    cf* const Sdst = MD::WRAP ? p.S_out : p.S;
 
     // prefetch registers: the pair's two rows (spectrum rows for the inverse-first modes, real rows for FWD) + Nyquist bins
     float4 sa[8], sb[8];
     cf nya = make_float2(0.f, 0.f), nyb = nya;
     auto load_pair = [&](int pb) {
-        const Rows r = rows_of(pb);
-        if (HAS_INV) {
+        const Rows r = rows_of<MD::WRAP>(p, pb, Yh);
+        if (MD::HAS_INV) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                sa[c] = *at(p.S, r.sa_, XP * 8, laneS, c * LG * 16);
-                sb[c] = *at(p.S, r.sb_, XP * 8, laneS, c * LG * 16);
+                sa[c] = *at<float4>(p.S, r.sa_, XP * 8, laneS, c * LG * 16);
+                sb[c] = *at<float4>(p.S, r.sb_, XP * 8, laneS, c * LG * 16);
             }
             nya = *reinterpret_cast<const cf*>(reinterpret_cast<const unsigned char*>(p.S) + r.sa_ * XP * 8 + (grp * XP * 8 + M * 8));
             nyb = *reinterpret_cast<const cf*>(reinterpret_cast<const unsigned char*>(p.S) + r.sb_ * XP * 8 + (grp * XP * 8 + M * 8));
         } else {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                sa[c] = *at(p.in, r.ra, X * 4, laneR, c * (G::BLK / 2) * 16);
-                sb[c] = *at(p.in, r.rb, X * 4, laneR, c * (G::BLK / 2) * 16);
+                sa[c] = *at<float4>(p.in, r.ra, X * 4, laneR, c * (G::BLK / 2) * 16);
+                sb[c] = *at<float4>(p.in, r.rb, X * 4, laneR, c * (G::BLK / 2) * 16);
             }
         }
     };
@@ -684,7 +460,7 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
         a.d2_c4 = opaque_i(a.d2_c4);
         a.d3_c4[0] = opaque_i(a.d3_c4[0]);
         a.d3_c4[1] = opaque_i(a.d3_c4[1]);
-        const Rows rw = rows_of(pb);
+        const Rows rw = rows_of<MD::WRAP>(p, pb, Yh);
         const cf wy = p.twy[rw.yy + grp];
         // the prefetch is unconditional (the last round re-reads its own pair): a conditional one would keep the old
         // registers alive through the whole body
@@ -697,21 +473,21 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
             xb[2 * c] = make_float2(sb[c].x, sb[c].y);
             xb[2 * c + 1] = make_float2(sb[c].z, sb[c].w);
         }
-        if (HAS_INV) {
+        if (MD::HAS_INV) {
             const cf nya_cur = nya, nyb_cur = nyb;  // this pair's Nyquist bins: the prefetch below overwrites the carried ones
-            if (MODE == INV_STORE || ARGMAX) load_pair(pnext);  // no epilogue operand: the next pair rides behind the whole inverse
+            if (MODE == INV_STORE || MD::ARGMAX) load_pair(pnext);  // no epilogue operand: the next pair rides behind the whole inverse
             // this pair's d / est rows ride behind the inverse transform, ahead of its last stage
             float4 auxa[8], auxb[8];
             auto load_aux_a = [&]() {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) auxa[r] = *at(p.aux, rw.sa_, X * 4, laneR, r * (G::BLK / 2) * 16);
+                for (int r = 0; r < 8; ++r) auxa[r] = *at<float4>(p.aux, rw.sa_, X * 4, laneR, r * (G::BLK / 2) * 16);
             };
             auto load_aux_b = [&]() {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) auxb[r] = *at(p.aux, rw.sb_, X * 4, laneR, r * (G::BLK / 2) * 16);
+                for (int r = 0; r < 8; ++r) auxb[r] = *at<float4>(p.aux, rw.sb_, X * 4, laneR, r * (G::BLK / 2) * 16);
             };
             pair_inv_head<LOGM>(xa, xb, nya_cur, nyb_cur, wy, ba, tw2, ut, l, a);
-            if (RATIO || UPDATE) {
+            if (MD::RATIO || MD::UPDATE) {
                 load_aux_a();
                 load_aux_b();
             }
@@ -721,8 +497,8 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
             const bool zero_plane = rw.zero;
             auto tail_row = [&](cf (&x)[16], const float4 (&aux)[8], const unsigned char* buf, long row) {
                 // CROP: this row's plane and row inside the unpadded output volume (64-bit division once per row, not per store)
-                const int zq = CROP ? (int)(row / p.Y) - p.wz.off : 0;
-                const long yq = CROP ? row % p.Y + grp : 0;
+                const int zq = MD::CROP ? (int)(row / p.Y) - p.wz.off : 0;
+                const long yq = MD::CROP ? row % p.Y + grp : 0;
                 get_dr<LOGM>(buf, x, a);
                 xw_fence();
                 stage_top1<LOGM, true>(x, tw1, l);
@@ -730,18 +506,8 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
                     float4 v = pack2(x[2 * r], x[2 * r + 1]);
-                    if (RATIO) {
-                        v.x = aux[r].x / fmaxf(v.x, p.eps);
-                        v.y = aux[r].y / fmaxf(v.y, p.eps);
-                        v.z = aux[r].z / fmaxf(v.z, p.eps);
-                        v.w = aux[r].w / fmaxf(v.w, p.eps);
-                    } else if (UPDATE) {
-                        v.x = fmaxf(aux[r].x * v.x, 0.0f);
-                        v.y = fmaxf(aux[r].y * v.y, 0.0f);
-                        v.z = fmaxf(aux[r].z * v.z, 0.0f);
-                        v.w = fmaxf(aux[r].w * v.w, 0.0f);
-                    }
-                    if (ARGMAX) {
+                    if (MD::RATIO || MD::UPDATE) v = value_op<MODE>(v, aux[r], p.eps);
+                    if (MD::ARGMAX) {
                         // four consecutive reals of row `row + grp`; a lane's indices do not ascend from pair to pair (row b
                         // lies Y/2 rows above row a), so ties are settled by the index
                         const float ax = fabsf(v.x), ay = fabsf(v.y), az = fabsf(v.z), aw = fabsf(v.w);
@@ -755,7 +521,7 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                             }
                         }
                     }
-                    if (CROP) {
+                    if (MD::CROP) {
                         // row = z Y + y of the box; the volume's plane z - wz.off, same y (Y is not padded), columns - wx.off
                         const int xq = 2 * r * G::BLK + 4 * l - p.wx.off;
                         if (zq >= 0 && zq < p.wz.n) {
@@ -770,7 +536,7 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                                     if (xq + e >= 0 && xq + e < p.wx.n) dst[e] = v4[e];
                             }
                         }
-                    } else if (STORE_REAL && !WRAP) *at_w(p.out, row, X * 4, laneR, r * (G::BLK / 2) * 16) = v;
+                    } else if (MD::STORE_REAL && !MD::WRAP) *at_w<float4>(p.out, row, X * 4, laneR, r * (G::BLK / 2) * 16) = v;
                     x[2 * r] = make_float2(v.x, v.y);
                     x[2 * r + 1] = make_float2(v.z, v.w);
                 }
@@ -785,8 +551,9 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                     for (int o = LG / 2; o > 0; o >>= 1) sd += __shfl_xor(sd, o, 64);
                     if (l == 0) p.rowsum[row + grp] = sd;
                 }
-                if (WRAP) {
-                    // Wrap-extension along x inside the row, as in fftconv_x3.inc: the epilogue's values are right on the volume's
+                if (MD::WRAP) {
+                    // Wrap-extension along x inside the row, as in fftconv_x3.inc and kept in step with it (why it is written out
+                    // per family: fftconv_xrows.inc): the epilogue's values are right on the volume's
                     // own voxels (box positions [off, off + n)); a margin position rel = pos - off in [-mlo, 0) takes the value
                     // of voxel rel + n, rel in [n, n + mhi) that of voxel rel - n, everything else is zero.  The two source
                     // strips travel through the start of the row's LDS buffer, free between the inverse's last read and the
@@ -829,16 +596,16 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                         for (int i = 0; i < 16; ++i) x[i] = make_float2(0.f, 0.f);
                     }
                     xw_fence();  // the scratch strips are read before the forward transform overwrites them
-                    if (STORE_REAL) {
+                    if (MD::STORE_REAL) {
 #pragma unroll
-                        for (int r = 0; r < 8; ++r) *at_w(p.out, row, X * 4, laneR, r * (G::BLK / 2) * 16) = pack2(x[2 * r], x[2 * r + 1]);
+                        for (int r = 0; r < 8; ++r) *at_w<float4>(p.out, row, X * 4, laneR, r * (G::BLK / 2) * 16) = pack2(x[2 * r], x[2 * r + 1]);
                     }
                 }
                 xw_fence();
             };
             tail_row(xa, auxa, ba, rw.ra);
             tail_row(xb, auxb, ba + G::ROWWORDS * 8, rw.rb);
-            if (MODE == INV_RATIO || MODE == INV_UPDATE || CROP) load_pair(pnext);
+            if (MODE == INV_RATIO || MODE == INV_UPDATE || MD::CROP) load_pair(pnext);
         } else if (p.norm_mean) {  // phase reconstruction: x / mean - 1 on the way in
             const float inv = (float)(1.0 / *p.norm_mean);
 #pragma unroll
@@ -853,11 +620,11 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
                 xa[2 * r + 1] = make_float2(fmaxf(xa[2 * r + 1].x, 0.f), fmaxf(xa[2 * r + 1].y, 0.f));
                 xb[2 * r] = make_float2(fmaxf(xb[2 * r].x, 0.f), fmaxf(xb[2 * r].y, 0.f));
                 xb[2 * r + 1] = make_float2(fmaxf(xb[2 * r + 1].x, 0.f), fmaxf(xb[2 * r + 1].y, 0.f));
-                *at_w(p.out, rw.ra, X * 4, laneR, r * (G::BLK / 2) * 16) = pack2(xa[2 * r], xa[2 * r + 1]);
-                *at_w(p.out, rw.rb, X * 4, laneR, r * (G::BLK / 2) * 16) = pack2(xb[2 * r], xb[2 * r + 1]);
+                *at_w<float4>(p.out, rw.ra, X * 4, laneR, r * (G::BLK / 2) * 16) = pack2(xa[2 * r], xa[2 * r + 1]);
+                *at_w<float4>(p.out, rw.rb, X * 4, laneR, r * (G::BLK / 2) * 16) = pack2(xb[2 * r], xb[2 * r + 1]);
             }
         }
-        if (HAS_FWD) {
+        if (MD::HAS_FWD) {
             xw_fence();  // not earlier: above the epilogue these 64 registers would sit on top of its operands
             load_pair(pnext);  // the next pair's rows ride behind the forward transform
             xw_fence();
@@ -867,8 +634,8 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
             // rows stored in (register pair, lane) order
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                *at_w(Sdst, rw.ra, XP * 8, laneS, c * LG * 16) = pack2(xa[2 * c], xa[2 * c + 1]);
-                *at_w(Sdst, rw.rb, XP * 8, laneS, c * LG * 16) = pack2(xb[2 * c], xb[2 * c + 1]);
+                *at_w<float4>(Sdst, rw.ra, XP * 8, laneS, c * LG * 16) = pack2(xa[2 * c], xa[2 * c + 1]);
+                *at_w<float4>(Sdst, rw.rb, XP * 8, laneS, c * LG * 16) = pack2(xb[2 * c], xb[2 * c + 1]);
             }
             if (l < 16) {  // Nyquist column (lane 0) + the zero pad columns of the row pitch
                 const cf zero = make_float2(0.f, 0.f);
@@ -879,7 +646,7 @@ __global__ __launch_bounds__(NT) void xw_kernel(Params p) {
             }
         }
     }
-    if (ARGMAX) {  // every wavefront writes its slot (one that had no pair: {-1, 0})
+    if (MD::ARGMAX) {  // every wavefront writes its slot (one that had no pair: {-1, 0})
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(best_v, o);
