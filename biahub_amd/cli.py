@@ -18,9 +18,9 @@ import numpy as np
 from . import parallel
 from .io import create_empty_plate, open_ome_zarr, process_single_position
 from .settings import (DeconvolveSettings, DeskewSettings, EstimateRegistrationSettings,
-                       EstimateStabilizationSettings, FlatFieldCorrectionSettings, FocusFindingSettings, PhaseCrossCorrSettings,
-                       ProcessingImportFuncSettings, PsfFromBeadsSettings, RegistrationSettings, RichardsonLucySettings,
-                       StabilizationSettings, StackRegSettings, StitchSettings)
+                       EstimateStabilizationSettings, EvalTransformSettings, FlatFieldCorrectionSettings, FocusFindingSettings,
+                       PhaseCrossCorrSettings, ProcessingImportFuncSettings, PsfFromBeadsSettings, RegistrationSettings,
+                       RichardsonLucySettings, StabilizationSettings, StackRegSettings, StitchSettings)
 from .utils.cluster import echo_resources, estimate_resources, get_submitit_cluster
 from .utils.config import model_to_yaml, settings_fingerprint, yaml_to_model
 from .utils.paths import get_output_paths, sbatch_to_submitit
@@ -589,6 +589,34 @@ def register_cli(source_position_dirpaths, target_position_dirpaths, config_file
     _run_positions("register", source_position_dirpaths, outs, job, Path(output_dirpath).parent)
 
 
+def _eval_transform_settings(block, T: int):
+    """``EvalTransformSettings`` of a config's ``eval_transform_settings`` block: ``None`` without the block, the defaults for an
+    empty one.  A store with fewer timepoints than either window is refused here, before anything is computed; the reference
+    raises ``Warning`` for it after all the estimates are made (registration/utils.py:339-359)."""
+    if block is None:
+        return None
+    ev = EvalTransformSettings(**block)
+    for field in ("validation_window_size", "interpolation_window_size"):
+        if T < getattr(ev, field):
+            raise click.UsageError(f"eval_transform_settings.{field} is {getattr(ev, field)} and the store has {T} timepoint(s): "
+                                   "transforms cannot be validated and interpolated over fewer timepoints than the window (the "
+                                   "reference raises here too, once every transform is estimated)")
+    return ev
+
+
+def _evaluate_transforms(transforms, shape_zyx, ev, verbose: bool, what: str):
+    """``evaluate_transforms`` with the settings ``ev``; an interpolation that cannot be made names ``what`` it was for."""
+    from .registration.utils import evaluate_transforms
+
+    try:
+        return evaluate_transforms(transforms=transforms, shape_zyx=shape_zyx, validation_window_size=ev.validation_window_size,
+                                   validation_tolerance=ev.validation_tolerance,
+                                   interpolation_window_size=ev.interpolation_window_size,
+                                   interpolation_type=ev.interpolation_type, verbose=verbose)
+    except (ValueError, Warning) as e:
+        raise click.UsageError(f"eval_transform_settings: the transforms of {what} cannot be interpolated: {e}") from None
+
+
 @cli.command("estimate-registration")
 @click.option("--source-position-dirpaths", "-s", multiple=True, required=True, callback=_positions)
 @click.option("--target-position-dirpaths", "-t", multiple=True, required=True, callback=_positions)
@@ -603,7 +631,10 @@ def estimate_registration_cli(source_position_dirpaths, target_position_dirpaths
     """Estimate the source -> target transform and save it as ``register`` / ``stabilize`` settings
     (reference: ``biahub estimate-registration``, estimate_registration.py:358-536).  ``estimation_method: ants``
     (Mattes-MI similarity estimate) and ``beads`` (bead detection, graph matching, point-set fit: registration/beads.py) run on the
-    GPU; ``manual`` (napari) is not part of this package."""
+    GPU; ``manual`` (napari) is not part of this package.  With ``eval_transform_settings`` a list of several transforms goes
+    through ``evaluate_transforms`` before it is saved (outliers against the rolling mean dropped, they and the timepoints
+    without a transform interpolated over time; ``verbose`` adds ``translation_plots/<method>_registration.png``); a single
+    transform needs no evaluation."""
 
     output_filepath = Path(output_filepath)
     output_dir = output_filepath.parent
@@ -622,6 +653,9 @@ def estimate_registration_cli(source_position_dirpaths, target_position_dirpaths
         source_channel_index = src.channel_names.index(source_channel_name)
         target_channel_index = tgt.channel_names.index(target_channel_name)
         voxel_size = list(tgt.scale)
+        source_shape_zyx = tuple(int(n) for n in src.data.shape[-3:])
+        T = int(src.data.shape[0])
+        eval_settings = _eval_transform_settings(settings.eval_transform_settings, T) if T > 1 else None
         if settings.estimation_method == "beads":
             from .registration.beads import estimate_tczyx
 
@@ -632,7 +666,7 @@ def estimate_registration_cli(source_position_dirpaths, target_position_dirpaths
                 sbatch_filepath=sbatch_filepath, output_folder_path=output_dir, ref_voxel_size=tuple(tgt.scale[-3:]),
                 mov_voxel_size=tuple(src.scale[-3:]))
             missing = [t for t, m in enumerate(transforms) if m is None]
-            if missing:  # the reference hands these to evaluate_transforms (eval_transform_settings), which is not part of this package
+            if missing and eval_settings is None:  # with the block (and more than one timepoint) evaluate_transforms fills them
                 raise click.UsageError(f"no transform could be estimated for timepoint(s) {missing} (empty data); "
                                        "interpolating over them (eval_transform_settings) is not available in biahub_amd")
         else:
@@ -643,16 +677,26 @@ def estimate_registration_cli(source_position_dirpaths, target_position_dirpaths
                 ref_channel_index=target_channel_index, ants_registration_settings=settings.ants_registration_settings,
                 affine_transform_settings=settings.affine_transform_settings, verbose=settings.verbose,
                 output_folder_path=output_dir, cluster="local", sbatch_filepath=sbatch_filepath)
+    rank0 = parallel.world_info()[0] == 0
     if len(transforms) == 1:
+        if settings.eval_transform_settings is not None:
+            click.echo("One transform was estimated, no need to evaluate")
         model = RegistrationSettings(source_channel_names=reg_sources, target_channel_name=reg_target,
                                      affine_transform_zyx=transforms[0])
     else:
+        if eval_settings is not None:  # estimate_registration.py:506-515; on every rank, so that each holds a complete model
+            transforms = _evaluate_transforms(transforms, source_shape_zyx, eval_settings, settings.verbose,
+                                              f"estimation_method {settings.estimation_method!r}")
         model = StabilizationSettings(stabilization_estimation_channel=target_channel_name, stabilization_type="affine",
                                       stabilization_method=settings.estimation_method,
                                       stabilization_channels=[source_channel_name, target_channel_name],
                                       affine_transform_zyx_list=transforms, time_indices="all",
                                       output_voxel_size=voxel_size)
-    if parallel.world_info()[0] == 0:
+    if rank0:
+        if len(transforms) > 1 and settings.verbose:
+            from .registration.utils import plot_translations
+
+            plot_translations(transforms, output_dir / "translation_plots" / f"{settings.estimation_method}_registration.png")
         model_to_yaml(model, output_filepath)
     click.echo(f"Registration settings saved to {output_dir.resolve()}")
 
@@ -710,7 +754,11 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
     ``stabilization_type: z`` (GPU mid-band power; ``z_stabilization_settings/<fov>.yml``, or ``average.yml`` with
     ``average_across_wells``), ``xy`` (StackReg translation of the in-focus planes on the GPU;
     ``xy_stabilization_settings/<fov>.yml``) and ``xyz`` (both; ``xyz_``, ``z_`` and ``xy_stabilization_settings/<fov>.yml``, xyz =
-    xy @ z per timepoint).  Each file feeds ``stabilize``."""
+    xy @ z per timepoint).  Each file feeds ``stabilize``.  With ``eval_transform_settings`` every list goes through
+    ``evaluate_transforms`` before it is saved (registration/utils.py: a transform that jumps away from the rolling mean of its
+    predecessors is dropped, the dropped ones and the timepoints without a transform are interpolated over time); a store with
+    fewer timepoints than one of its windows is refused before anything is computed.  With ``verbose`` the translations over
+    time are plotted to ``translation_plots/<fov>.png`` (``beads.png`` for beads)."""
     from .estimate_stabilization import (estimate_xy_stabilization, estimate_xyz_stabilization_pcc, estimate_z_stabilization,
                                          save_transforms)
 
@@ -722,14 +770,21 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
         raise click.UsageError(f"stabilization_type {settings.stabilization_type!r} with method "
                                f"{settings.stabilization_method!r} is not available in biahub_amd (only 'xyz' with "
                                "'phase-cross-corr' or 'beads' and 'z', 'xy' or 'xyz' with 'focus-finding').")
-    if settings.eval_transform_settings:
-        raise click.UsageError("eval_transform_settings (transform validation / interpolation) is not available in biahub_amd")
-    output_dirpath = Path(output_dirpath)
-    output_dirpath.mkdir(parents=True, exist_ok=True)
     with open_ome_zarr(input_position_dirpaths[0]) as ds:
         channel_index = ds.channel_names.index(settings.stabilization_estimation_channel)
         voxel_size = list(ds.scale)
-        fov_yx = tuple(int(n) for n in ds.data.shape[-2:])
+        shape_zyx = tuple(int(n) for n in ds.data.shape[-3:])
+        fov_yx = shape_zyx[-2:]
+        eval_settings = _eval_transform_settings(settings.eval_transform_settings, int(ds.data.shape[0]))
+    output_dirpath = Path(output_dirpath)
+    output_dirpath.mkdir(parents=True, exist_ok=True)
+    plots_dirpath = output_dirpath / "translation_plots"
+
+    def evaluated(transforms, what):
+        if eval_settings is None:
+            return transforms
+        return _evaluate_transforms(transforms, shape_zyx, eval_settings, settings.verbose, what)
+
     if combo in (("z", "focus-finding"), ("xyz", "focus-finding")):
         from .estimate_stabilization import centre_window
 
@@ -770,17 +825,19 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
         if transforms and transforms[0] is None:  # with propagation timepoint 0 is not estimated: it is its own reference
             transforms[0] = np.eye(4).tolist()
         missing = [t for t, m in enumerate(transforms) if m is None]
-        if missing:  # the reference hands these to evaluate_transforms (eval_transform_settings), refused above
+        if missing and eval_settings is None:  # with the block evaluate_transforms fills them, as in the reference (:1427-1436)
             raise click.UsageError(f"no transform could be estimated for timepoint(s) {missing} (empty data); "
                                    "interpolating over them (eval_transform_settings) is not available in biahub_amd")
         if parallel.world_info()[0] == 0:
+            transforms = evaluated(transforms, f"FOV {'/'.join(Path(input_position_dirpaths[0]).parts[-3:])} (beads)")
             model = StabilizationSettings(stabilization_type=settings.stabilization_type,
                                           stabilization_method=settings.stabilization_method,
                                           stabilization_estimation_channel=settings.stabilization_estimation_channel,
                                           stabilization_channels=settings.stabilization_channels,
                                           affine_transform_zyx_list=[np.eye(4).tolist()], time_indices="all",
                                           output_voxel_size=voxel_size)
-            save_transforms(model, transforms, output_dirpath / "xyz_stabilization_settings.yml")
+            save_transforms(model, transforms, output_dirpath / "xyz_stabilization_settings.yml",
+                            output_filepath_plot=plots_dirpath / "beads.png", verbose=settings.verbose)
         click.echo(f"Stabilization settings saved to {output_dirpath.resolve()}")
         return
     if combo == ("xyz", "phase-cross-corr"):
@@ -816,15 +873,21 @@ def estimate_stabilization_cli(input_position_dirpaths, output_dirpath, config_f
         written["z"] = {fov: z_transforms[fov] for fov in fov_transforms}
         written["xy"] = {fov: xy_transforms[fov] for fov in fov_transforms}
     if parallel.world_info()[0] == 0:
+        # every list on its own, the xyz product too: it is not recomposed from the evaluated parts (reference :1329-1360).
+        # All of them before the first file, so that a list that cannot be interpolated leaves nothing half written.
+        written = {kind: {fov: evaluated(transforms, f"FOV {fov} ({kind})") for fov, transforms in per_fov.items()}
+                   for kind, per_fov in written.items()}
         for kind, per_fov in written.items():
             for fov, transforms in per_fov.items():
+                plot = plots_dirpath / f"{fov}.png" if kind == settings.stabilization_type else None  # none for the parts of xyz
                 model = StabilizationSettings(stabilization_type=settings.stabilization_type,
                                               stabilization_method=settings.stabilization_method,
                                               stabilization_estimation_channel=settings.stabilization_estimation_channel,
                                               stabilization_channels=settings.stabilization_channels,
                                               affine_transform_zyx_list=[np.eye(4).tolist()], time_indices="all",
                                               output_voxel_size=voxel_size)
-                save_transforms(model, transforms, output_dirpath / f"{kind}_stabilization_settings" / f"{fov}.yml")
+                save_transforms(model, transforms, output_dirpath / f"{kind}_stabilization_settings" / f"{fov}.yml",
+                                output_filepath_plot=plot, verbose=settings.verbose)
     click.echo(f"Stabilization settings saved to {output_dirpath.resolve()}")
 
 

@@ -589,9 +589,11 @@ def estimate_xy_stabilization(input_position_dirpaths, output_folder_path, stack
 
 
 def save_transforms(model, transforms, output_filepath_settings, output_filepath_plot=None, verbose: bool = False):
-    """``registration/utils.py:370-422`` without the plot."""
+    """``registration/utils.py:370-422``: the settings file, and with ``verbose`` and a plot path the translations over time as
+    a png."""
     from pathlib import Path
 
+    from .registration.utils import plot_translations
     from .utils.config import model_to_yaml
 
     if transforms is None or len(transforms) == 0:
@@ -604,3 +606,9 @@ def save_transforms(model, transforms, output_filepath_settings, output_filepath
         output_filepath_settings = output_filepath_settings.with_suffix(".yml")
     output_filepath_settings.parent.mkdir(parents=True, exist_ok=True)
     model_to_yaml(model, output_filepath_settings)
+    if verbose and output_filepath_plot is not None:
+        output_filepath_plot = Path(output_filepath_plot)
+        if output_filepath_plot.suffix not in [".png"]:
+            output_filepath_plot = output_filepath_plot.with_suffix(".png")
+        output_filepath_plot.parent.mkdir(parents=True, exist_ok=True)
+        plot_translations(np.asarray(transforms), output_filepath_plot)

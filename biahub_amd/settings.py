@@ -313,10 +313,20 @@ class StackRegSettings(_Strict):
     t_reference: Literal["first", "previous"] = "first"
 
 
+class EvalTransformSettings(_Strict):
+    """biahub/settings.py:233-237: the windows and the tolerance of ``registration.utils.evaluate_transforms``."""
+
+    validation_window_size: int = 10
+    validation_tolerance: float = 1000.0
+    interpolation_window_size: int = 3
+    interpolation_type: Literal["linear", "cubic"] = "linear"
+
+
 class EstimateStabilizationSettings(_Strict):
     """biahub/settings.py:295-333; ``phase-cross-corr`` (xyz), ``beads`` (xyz) and ``focus-finding`` (z, xy, xyz) run in this
-    package.  ``stack_reg_settings`` and ``focus_finding_settings`` are carried as plain dicts and validated into
-    ``StackRegSettings`` and ``FocusFindingSettings`` where they are used (``None``: the defaults)."""
+    package.  ``stack_reg_settings``, ``focus_finding_settings`` and ``eval_transform_settings`` are carried as plain dicts and
+    validated into ``StackRegSettings``, ``FocusFindingSettings`` and ``EvalTransformSettings`` where they are used (``None``:
+    the defaults; for ``eval_transform_settings``, ``None`` is no evaluation and an empty block the defaults)."""
 
     stabilization_estimation_channel: str
     stabilization_channels: list
