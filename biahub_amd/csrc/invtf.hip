@@ -327,7 +327,23 @@ struct OpticsGeo {
     int invert;              // z positions flipped (invert_phase_contrast)
 };
 
-__device__ __forceinline__ double fft_freq(int i, int n, double d) { return (double)(i < (n + 1) / 2 ? i : i - n) / ((double)n * d); }
+// np.fft.fftfreq / torch.fft.fftfreq: k * (1 / (n d)), the reciprocal rounded first (k / (n d) is an ulp off at some k)
+__device__ __forceinline__ double fft_freq(int i, int n, double d) {
+#pragma clang fp contract(off)
+    const double step = 1.0 / ((double)n * d);
+    return (double)(i < (n + 1) / 2 ? i : i - n) * step;
+}
+// Radial frequency of plane bin (y, x), waveorder util.generate_radial_frequencies: sqrt(fy^2 + fx^2) with each square rounded
+// on its own, as numpy forms it.  A bin sits inside a pupil when this is < NA / wavelength, and a cut-off may land exactly on
+// one of these values: a fused multiply-add (which the compiler forms wherever contraction is allowed, __dmul_rn / __dadd_rn
+// included) moves the sum by an ulp at many bins and such a bin to the other side of the comparison — and with it the pupil
+// count that scales every bin of the result.  The one helper of every kernel that asks for pupil membership.
+__device__ __forceinline__ double radial_freq(int y, int x, int Y, int X, double yx_px) {
+#pragma clang fp contract(off)
+    const double fy = fft_freq(y, Y, yx_px), fx = fft_freq(x, X, yx_px);
+    const double yy = fy * fy, xx = fx * fx;
+    return sqrt(yy + xx);
+}
 // z position of plane zi: ifftshift((arange(Zt) - Zt // 2) * dz), optionally flipped
 __device__ __forceinline__ double z_position(int zi, const OpticsGeo& g) {
     if (g.invert) zi = g.Zt - 1 - zi;
@@ -345,8 +361,7 @@ __global__ __launch_bounds__(256) void optics_planes_kernel(cf* __restrict__ A, 
         const int zi = (int)(i / plane);
         const int64_t r = i - (int64_t)zi * plane;
         const int y = (int)(r / g.X), x = (int)(r - (int64_t)y * g.X);
-        const double fy = fft_freq(y, g.Y, g.yx_px), fx = fft_freq(x, g.X, g.yx_px);
-        const double frr = sqrt(fx * fx + fy * fy);
+        const double frr = radial_freq(y, x, g.Y, g.X, g.yx_px);
         const double det = frr < g.cut_det ? 1.0 : 0.0, ill = frr < g.cut_ill ? 1.0 : 0.0;
         const double lamb = 1.0 / g.inv_lamb;
         const double ob = sqrt(fmax(1.0 - lamb * lamb * frr * frr, 0.0) * det) * g.inv_lamb;  // oblique factor
@@ -403,8 +418,7 @@ __global__ void pupil_count_kernel(OpticsGeo g, unsigned long long* count) {
     unsigned long long c = 0;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < plane; r += (int64_t)gridDim.x * blockDim.x) {
         const int y = (int)(r / g.X), x = (int)(r - (int64_t)y * g.X);
-        const double fy = fft_freq(y, g.Y, g.yx_px), fx = fft_freq(x, g.X, g.yx_px);
-        const double frr = sqrt(fx * fx + fy * fy);
+        const double frr = radial_freq(y, x, g.Y, g.X, g.yx_px);
         c += (frr < g.cut_det && frr < g.cut_ill) ? 1ull : 0ull;
     }
     if (c) atomicAdd(count, c);

@@ -68,6 +68,28 @@ PCC_NORM_RMS_TOL = 3e-5
 PCC_NORM_VOXEL_TOL = 6e-2
 PCC_NORM_RMS_TOL_WHITE = 5e-5
 
+# The transfer functions of compute-tf (bh_phase_transfer_function_3d, bh_fluorescence_transfer_function_3d;
+# tests/test_gpu_tf_f64.py) against oracle_np.wo_*_transfer_function_3d in complex128, each complex array weighed as a real one of
+# shape (Z, Y, X, 2), the real- and the imaginary-potential function each on its own scale.  Same rule: 10x the error of the
+# float32 / complex64 restatement (tests/tf_cases.py: phase_c64, fluorescence_c64 — pupils, phases and Green's function formed in
+# float64 and rounded, as the kernel documents, everything after that in complex64) against float64, measured on the CPU at
+# every case of the GPU tests, the pupil ties among them (tests/test_tf_reference.py holds the restatement to a tenth of these
+# bounds), never from the GPU's output.
+#   rms_rel:   phase 8.7e-8 .. 3.9e-7 (worst: the imaginary potential at (4, 1030, 1027); 3.7e-7 at (3, 730, 727), <= 2.5e-7
+#              below 10^6 bins), fluorescence 1.0e-7 .. 2.3e-7: RMS_TOL stands for both.
+#   voxel_rel: a transfer function falls to nothing towards the edge of its support, so the quotient is in effect
+#              max error / (0.01 rms) on the weak bins, and grows with the number of planes the rms is spread over.  Phase
+#              1.8e-5 .. 3.0e-4 (worst: (512, 12, 14), imaginary potential; 2.0e-4 at (4, 1030, 1027), 1.7e-4 at (35, 150, 202),
+#              <= 1.3e-4 elsewhere); fluorescence 4.3e-5 .. 5.3e-4 (worst: (35, 150, 202); 2.6e-4 at (512, 12, 14), <= 1.2e-4
+#              elsewhere).  The two models differ 1.8x, less than a factor of two: one bound, 10x the worst, rounded up.
+TF_RMS_TOL = RMS_TOL
+TF_VOXEL_TOL = 6e-3
+# With at most three planes in all (Zt = 1, or Zt = 3 whose window is (1, 0, 0)) only the plane z = 0 is kept, H1 = -H2 and the
+# real-potential function is zero but for rounding: 1e-16 of the imaginary one in float64, so no relative metric applies.  It is
+# held to max|re| / max|im| instead.  The restatement's cancellation leaves 0 .. 2.2e-7 (0 at (1, 12, 10) + pad 1, 4.9e-8 .. 9.8e-8
+# on planes up to 64 wide, worst at (3, 730, 727): the residue grows with the length of the plane transforms): 10x, rounded up.
+TF_ZERO_RE_RATIO_TOL = 3e-6
+
 
 # (rms, voxel) by class — the four derivations above, in their order
 PCC_BOUNDS = {
