@@ -15,7 +15,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / "libbhcore.so"
 
 BH_OK, BH_ERR_INVALID, BH_ERR_HIP, BH_ERR_NOMEM, BH_ERR_UNSUPPORTED = range(5)
-DT_U8, DT_U16, DT_F32, DT_I16, DT_F16 = 0, 1, 2, 3, 4  # DT_F16: only as out_dtype of bh_stitch_blend
+DT_U8, DT_U16, DT_F32, DT_I16, DT_F16, DT_U32 = 0, 1, 2, 3, 4, 5  # DT_F16: stitch's out_dtype and pyramid; DT_U32: pyramid only
 FILL_NONE, FILL_CONSTANT, FILL_MEAN = 0, 1, 2
 INTERP_NEAREST, INTERP_LINEAR, INTERP_CUBIC = 0, 1, 3
 BOUNDARY_ITK, BOUNDARY_SCIPY_CONSTANT, BOUNDARY_ZEROS = 0, 1, 2

@@ -1,9 +1,9 @@
 // Multiscale pyramid levels (biahub/pyramid.py: iohub's Position.compute_pyramid): level k of a (Z, Y, X) volume has extents
 // n_k = ceil(n_{k-1} / 2) and voxel (z, y, x) reduces the block [2z, min(2z + 2, n)) x [2y, ...) x [2x, ...) of level k-1 AS
 // STORED (rounded to the dtype): 1, 2, 4 or 8 elements, partial blocks at the upper edges unpadded.  Methods:
-// stride (the block's first element), mean (integers: exact sum, quotient rounded to nearest, ties to even; float32: float64
-// sum in (z, y, x) order, one rounding), min, max, median (the lower one: sorted[(count - 1) / 2]), mode (most frequent,
-// smallest among ties).
+// stride (the block's first element), mean (integers: exact sum, quotient rounded to nearest, ties to even, the sum of uint32
+// held in 64 bits; float32 and float16: float64 sum in (z, y, x) order, one rounding from float64 to the dtype), min, max, median
+// (the lower one: sorted[(count - 1) / 2]), mode (most frequent, smallest among ties).  float16 compares as float32 does.
 //
 // One launch reads its source level once and writes the next D <= 3 levels.  A thread owns an aligned source box of
 // 2^D (z) x 2^D (y) x E (x) voxels, E = max(2^D, 16 B / element): the cascade nests because ceil nests, so every block of every
@@ -11,6 +11,8 @@
 // four level-(k-1) rows under it, stored, and handed up; at most 4 rows per level are live.  A workgroup is 4 boxes along y by
 // 64 along x, so a wave reads 64 * E contiguous elements per row.  Boxes wholly inside the source skip every per-voxel test;
 // rows whose byte offsets are not multiples of the access width go element by element (a per-level, launch-uniform flag).
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace bh {
@@ -32,6 +34,11 @@ template <> struct Lim<uint8_t> { __device__ static uint8_t hi() { return 0xFF; 
 template <> struct Lim<uint16_t> { __device__ static uint16_t hi() { return 0xFFFF; } };
 template <> struct Lim<int16_t> { __device__ static int16_t hi() { return 0x7FFF; } };
 template <> struct Lim<float> { __device__ static float hi() { return INFINITY; } };
+template <> struct Lim<_Float16> { __device__ static _Float16 hi() { return (_Float16)INFINITY; } };
+template <> struct Lim<uint32_t> { __device__ static uint32_t hi() { return 0xFFFFFFFFu; } };
+
+template <typename T>
+constexpr bool is_floating = std::is_same<T, float>::value || std::is_same<T, _Float16>::value;
 
 // N elements at p: 16-, 8-, 4- or 2-byte accesses when `vec` (the row offset is a multiple of min(N * sizeof(T), 16) bytes),
 // element by element otherwise
@@ -114,21 +121,27 @@ __device__ __forceinline__ T reduce_block(const T (&v)[8], int cz, int cy, int c
         return r;
     } else if constexpr (M == DS_MEAN) {
         if (cz <= 0 || cy <= 0 || cx <= 0) return T(0);
-        if constexpr (sizeof(T) == 4) {  // float32
+        if constexpr (is_floating<T>) {
             double s = 0.0;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
                 if (ok[i]) s += (double)v[i];
-            return (float)(s / (double)(cz * cy * cx));
+            const double q = s / (double)(cz * cy * cx);
+            // float64 -> binary16 directly, ONE rounding: through float32, 1 + 2^-11 + 2^-27 goes to 1 + 2^-11 and then, a tie,
+            // to 1, while the nearest binary16 is 1 + 2^-10.  gfx950 has no such instruction; the compiler expands the cast in
+            // integer arithmetic on the float64's words (no fast-math: DESIGN.md §3.6).  For finite float16 inputs the sum and
+            // the quotient (count 1, 2, 4, 8) are exact, so this is the exact mean rounded once.
+            return (T)q;
         } else {
-            int s = 0;
+            using S = typename std::conditional<sizeof(T) == 4, int64_t, int>::type;  // eight uint32 overflow an int
+            S s = 0;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                if (ok[i]) s += (int)v[i];
+                if (ok[i]) s += (S)v[i];
             const int sh = (cz - 1) + (cy - 1) + (cx - 1);  // count = 2^sh
-            int q = s >> sh;                                 // floor, also for negative sums
+            S q = s >> sh;                                   // floor, also for negative sums
             if (sh > 0) {
-                const int r = s - (q << sh), half = 1 << (sh - 1);
+                const S r = s - (q << sh), half = S(1) << (sh - 1);
                 q += (r > half) | ((r == half) & (q & 1));  // to nearest, ties to even
             }
             return (T)q;
@@ -299,8 +312,9 @@ using namespace bh;
 
 extern "C" int bh_pyramid_downsample(bh_ctx* ctx, const void* in, int dtype, int64_t Z, int64_t Y, int64_t X, int method, int n,
                                      void* const* out) {
-    BH_REQUIRE(dtype == BH_DT_U8 || dtype == BH_DT_U16 || dtype == BH_DT_I16 || dtype == BH_DT_F32,
-               "bh_pyramid_downsample: unsupported dtype code %d (uint8, uint16, int16, float32)", dtype);
+    BH_REQUIRE(dtype == BH_DT_U8 || dtype == BH_DT_U16 || dtype == BH_DT_I16 || dtype == BH_DT_F32 || dtype == BH_DT_F16 ||
+                   dtype == BH_DT_U32,
+               "bh_pyramid_downsample: unsupported dtype code %d (uint8, uint16, int16, float32, float16, uint32)", dtype);
     BH_REQUIRE(method >= BH_DS_STRIDE && method <= BH_DS_MODE, "bh_pyramid_downsample: unknown method code %d", method);
     BH_REQUIRE(n >= 1, "bh_pyramid_downsample: n = %d levels to write (>= 1)", n);
     BH_REQUIRE(Z > 0 && Y > 0 && X > 0, "bh_pyramid_downsample: bad shape (%lld, %lld, %lld)", (long long)Z, (long long)Y,
@@ -324,7 +338,10 @@ extern "C" int bh_pyramid_downsample(bh_ctx* ctx, const void* in, int dtype, int
             case BH_DT_U8: BH_TRY(launch_dtype<uint8_t>(ctx, a, method, depth)); break;
             case BH_DT_U16: BH_TRY(launch_dtype<uint16_t>(ctx, a, method, depth)); break;
             case BH_DT_I16: BH_TRY(launch_dtype<int16_t>(ctx, a, method, depth)); break;
-            default: BH_TRY(launch_dtype<float>(ctx, a, method, depth)); break;
+            case BH_DT_F32: BH_TRY(launch_dtype<float>(ctx, a, method, depth)); break;
+            case BH_DT_F16: BH_TRY(launch_dtype<_Float16>(ctx, a, method, depth)); break;
+            case BH_DT_U32: BH_TRY(launch_dtype<uint32_t>(ctx, a, method, depth)); break;
+            default: BH_REQUIRE(false, "bh_pyramid_downsample: unsupported dtype code %d", dtype);
         }
         src = a.out[depth - 1];
         z = a.Z[depth], y = a.Y[depth], x = a.X[depth];

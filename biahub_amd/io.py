@@ -83,7 +83,7 @@ def _torch_dtype(dtype):
 
         _TORCH_DT = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16, np.dtype(np.int16): torch.int16,
                      np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
-                     np.dtype(np.float16): torch.float16}
+                     np.dtype(np.float16): torch.float16, np.dtype(np.uint32): torch.uint32}
     return _TORCH_DT.get(np.dtype(dtype))
 
 
@@ -581,7 +581,10 @@ class ZarrArray:
             h = heads[i]
             dst = out8[z0 * plane:min(Z, z0 + iz) * plane]
             if h is None:
-                out[z0:z0 + iz] = self.fill_value
+                if tdt == torch.uint32:  # torch fills no uint32 tensor: the same bits through int32
+                    out.view(torch.int32)[z0:z0 + iz] = int(np.array(self.fill_value, np.uint32).view(np.int32))
+                else:
+                    out[z0:z0 + iz] = self.fill_value
                 continue
             mode = codecs.BLOSC_NOSHUFFLE if h.memcpyed else h.shuffle_mode
             src = dstage[i * cbytes:(i + 1) * cbytes]

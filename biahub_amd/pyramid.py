@@ -18,7 +18,7 @@ from . import _lib
 METHODS = ("stride", "median", "mode", "mean", "min", "max")  # the reference's click.Choice (pyramid.py:55-71)
 _METHOD_CODE = {"stride": _lib.DS_STRIDE, "mean": _lib.DS_MEAN, "min": _lib.DS_MIN, "max": _lib.DS_MAX,
                 "median": _lib.DS_MEDIAN, "mode": _lib.DS_MODE}
-DTYPES = ("uint8", "uint16", "int16", "float32")
+DTYPES = ("uint8", "uint16", "int16", "float32", "float16", "uint32")
 
 
 def level_shapes(shape, levels: int) -> list[tuple[int, int, int]]:
@@ -29,15 +29,28 @@ def level_shapes(shape, levels: int) -> list[tuple[int, int, int]]:
     return out
 
 
+def _dtype_name(dtype) -> str:
+    """"uint16" for np.dtype("uint16"), np.uint16 and torch.uint16 alike; anything numpy cannot name keeps its own text."""
+    text = str(dtype)
+    if text.startswith("torch."):
+        return text[len("torch."):]
+    import numpy as np
+
+    try:
+        return np.dtype(dtype).name
+    except TypeError:
+        return text
+
+
 def check_args(dtype, levels: int, method: str) -> None:
     """The host-side checks of ``downsample_pyramid``, usable before any read: ValueError naming what is wrong."""
     if method not in _METHOD_CODE:
         raise ValueError(f"pyramid method {method!r}: expected one of {', '.join(METHODS)}")
     if int(levels) < 1:
         raise ValueError(f"levels = {levels}: the pyramid has at least level 0")
-    name = str(dtype).replace("torch.", "")
+    name = _dtype_name(dtype)
     if name not in DTYPES:
-        raise ValueError(f"pyramid: dtype {name} is not supported (uint8, uint16, int16, float32)")
+        raise ValueError(f"pyramid: dtype {name} is not supported ({', '.join(DTYPES)})")
 
 
 def downsample_pyramid(vol, levels: int, method: str = "mean") -> list:
@@ -60,7 +73,8 @@ def downsample_pyramid(vol, levels: int, method: str = "mean") -> list:
     outs = [empty(s, src.dtype, dev) for s in shapes[1:]]
     ctx = get_context(dev)
     arr = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-    code = {torch.uint8: _lib.DT_U8, torch.uint16: _lib.DT_U16, torch.int16: _lib.DT_I16, torch.float32: _lib.DT_F32}[src.dtype]
+    code = {torch.uint8: _lib.DT_U8, torch.uint16: _lib.DT_U16, torch.int16: _lib.DT_I16, torch.float32: _lib.DT_F32,
+            torch.float16: _lib.DT_F16, torch.uint32: _lib.DT_U32}[src.dtype]
     Z, Y, X = shapes[0]
     _lib.check(ctx.lib.bh_pyramid_downsample(ctx.handle, ptr(src), code, Z, Y, X, _METHOD_CODE[method], len(outs), arr))
     return outs

@@ -97,7 +97,8 @@ extern "C" {
 #define BH_DT_U16 1
 #define BH_DT_F32 2
 #define BH_DT_I16 3
-#define BH_DT_F16 4 /* IEEE binary16; accepted only as out_dtype of bh_stitch_blend */
+#define BH_DT_F16 4 /* IEEE binary16; accepted as out_dtype of bh_stitch_blend and as dtype of bh_pyramid_downsample */
+#define BH_DT_U32 5 /* label images; accepted only as dtype of bh_pyramid_downsample */
 
 /* overhang fill modes (biahub/deskew.py:538-540) */
 #define BH_FILL_NONE 0
@@ -172,15 +173,18 @@ int bh_bin_finish(bh_ctx* ctx, const float* v, int64_t n, int apply, float sub, 
 
 /* ---- multiscale pyramid levels (biahub/pyramid.py: iohub's Position.compute_pyramid) ---------------- */
 #define BH_DS_STRIDE 0 /* the block's first element: level k = level0[::2^k, ::2^k, ::2^k]                          */
-#define BH_DS_MEAN 1   /* integers: exact sum / count, to nearest, ties to even; float32: float64 sum in (z, y, x) order */
+#define BH_DS_MEAN 1   /* integers: exact sum / count, to nearest, ties to even (uint32: the sum in 64 bits); float32 and
+                        * float16: float64 sum in (z, y, x) order / count, rounded ONCE from float64 to the dtype */
 #define BH_DS_MIN 2
 #define BH_DS_MAX 3
 #define BH_DS_MEDIAN 4 /* the lower median: sorted block[(count - 1) / 2]                                              */
 #define BH_DS_MODE 5   /* the most frequent value, the smallest among ties                                              */
 /* out[k-1] (device, (ceil(Z / 2^k), ceil(Y / 2^k), ceil(X / 2^k)) of the input dtype) receives level k, k = 1..n.  Level k
  * voxel (z, y, x) reduces the block [2z, min(2z + 2, n)) x [2y, ...) x [2x, ...) of level k-1 as stored (1, 2, 4 or 8
- * elements).  in (device, (Z, Y, X), BH_DT_*) is only read.  BH_ERR_INVALID for an unknown dtype or method, n < 1, a
- * non-positive extent or a null pointer, before any device call.  Stream-ordered, no allocation, does not synchronise. */
+ * elements).  in (device, (Z, Y, X)) is only read; dtype is BH_DT_U8, _U16, _I16, _F32, _F16 or _U32.  float16 values
+ * compare as their float32 widenings do (min, max, median, mode); the float16 mean never passes through float32 (two
+ * roundings give other bits).  BH_ERR_INVALID for any other dtype code, an unknown method, n < 1, a non-positive extent
+ * or a null pointer, before any device call.  Stream-ordered, no allocation, does not synchronise. */
 int bh_pyramid_downsample(bh_ctx* ctx, const void* in, int dtype, int64_t Z, int64_t Y, int64_t X, int method, int n,
                           void* const* out);
 

@@ -23,7 +23,7 @@ ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--levels", type=int, default=4)
 ap.add_argument("--cli", action="store_true", help="time the per-position job on Blosc-zstd and Blosc-lz4 stores instead")
 ap.add_argument("--methods", nargs="*", default=["stride", "mean", "min", "max", "median", "mode"])
-ap.add_argument("--dtypes", nargs="*", default=["float32", "uint16"])
+ap.add_argument("--dtypes", nargs="*", default=["float32", "uint16"], help="also float16, uint32, int16")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 
@@ -51,6 +51,10 @@ def kernel_bench():
         dt = getattr(torch, dname)
         if dt == torch.float32:
             vol = torch.rand(args.shape, generator=g, device=dev) * 1000
+        elif dt == torch.float16:  # positive finite bit patterns, subnormals included
+            vol = torch.randint(0, 0x7BFF, args.shape, generator=g, device=dev, dtype=torch.int16).view(dt)
+        elif dt == torch.uint32:  # a few labels
+            vol = torch.randint(0, 5, args.shape, generator=g, device=dev, dtype=torch.int32).view(dt)
         else:
             vol = torch.randint(0, 4096, args.shape, generator=g, device=dev, dtype=torch.int16).view(dt)
         s = vol.element_size()
